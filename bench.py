@@ -15,7 +15,7 @@ connections and broadcasts the compiled tables over RCCL (the other ranks
 install them without compiling: l7g_tables_import), and the stream is sharded by connection (whole connections per rank,
 each protocol's bytes balanced over ranks: cilium_amd/dist.py).  Each rank
 tiles its shard up to the per-GPU request count (weak scaling), classifies it
-every step and all-reduces the counters.  Every rank checks every verdict of
+every step and all-reduces the counters.  With --full every rank checks every verdict of
 its last step against the oracle's verdicts for its shard; the mismatch count
 is summed over ranks.
 
@@ -26,7 +26,19 @@ is summed over ranks.
   cfg4  10k HTTP rules, 512 identities   10M HTTP requests (1M unique, tiled)
   cfg5  mixed HTTP/Kafka/memcached       100M requests (2M unique, tiled; default)
 
-Besides the device-resident rate (`value`) the line reports:
+A plain run sets up, warms up, times the steps and prints the line: the
+device-resident rate (`value`), `ms_per_step`, the step's scanned GB/s and the
+counter totals.  --dump-outputs DIR then also writes what the last timed step
+left in the caller's output arrays (verdict.npy float32; rule.npy and
+consumed.npy float64; a fixed seeded sample of the requests when there are more
+than DUMP_MAX of them, rank 0's shard when N > 1) and the accumulated
+counters (counters.npy float64).  The inputs come from fixed seeds, so two
+builds run with the same arguments can be compared output for output.
+
+With --full the run also checks and measures the following (each leg can be
+switched off on its own with its --no-* option):
+  * parity     -- every verdict, rule id and consumed length of the last step
+                  on every rank against the oracle;
   * roofline   -- the dominant kernel's algorithmic bytes / its device time
                   (HIP events around each launch, on the launch stream);
   * kernels    -- the same per kernel of the step;
@@ -49,7 +61,7 @@ Besides the device-resident rate (`value`) the line reports:
                   (tests/native/latency_main.cc), next to the oracle deciding
                   one request per call on one core.
 
-Usage:  python bench.py [--gpus N --steps K --warmup W --workload cfgX]
+Usage:  python bench.py [--gpus N --steps K --warmup W --workload cfgX] [--full] [--dump-outputs DIR]
         (N > 1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
 Rank 0 prints one JSON line.
 """
@@ -66,6 +78,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E peak (/opt/skills/guides/MI355X_MICROARCH.md)
 METRIC = "L7 verdicts/sec + scanned GB/s (HBM roofline frac), 1/2/4/8 MI355X"
+DUMP_MAX = 2_000_000  # --dump-outputs: requests written (4 + 8 + 8 bytes each: 40 MB)
+DUMP_SEED = 20240605
 
 # workload -> (default requests per GPU, default unique requests, description)
 WORKLOADS = {
@@ -317,6 +331,22 @@ def latency_leg(gen, refpy, iters=2000):
     return out
 
 
+def dump_outputs(torch, path, n, outs, totals):
+    """The caller's output arrays as the last timed step left them, as
+    path/<name>.npy: every request when n <= DUMP_MAX, else the same seeded
+    sample of DUMP_MAX request indices (ascending) in every run."""
+    os.makedirs(path, exist_ok=True)
+    idx = None
+    if n > DUMP_MAX:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX))
+        idx = torch.from_numpy(idx).to(outs[0].device)
+    v, r, c = (t.cpu().numpy() if idx is None else t.index_select(0, idx).cpu().numpy() for t in outs)
+    np.save(os.path.join(path, "verdict.npy"), v.astype(np.float32))
+    np.save(os.path.join(path, "rule.npy"), r.astype(np.float64))
+    np.save(os.path.join(path, "consumed.npy"), c.view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, "counters.npy"), totals.cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -330,8 +360,15 @@ def main():
     ap.add_argument("--no-latency", action="store_true")
     ap.add_argument("--no-streams", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0, help="oracle threads (0 = every usable core)")
-    ap.add_argument("--profile-steps", type=int, default=3, help="extra steps with per-kernel HIP events")
+    ap.add_argument("--profile-steps", type=int, default=3, help="extra steps with per-kernel HIP events (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity check against the oracle, the per-kernel roofline steps, the e2e, "
+                         "streams and latency legs and the CPU baseline (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -445,9 +482,12 @@ def main():
     elapsed = time.perf_counter() - t_start
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, n, (d_v, d_r, d_c), totals)
+
     # per-kernel device time: extra steps with HIP events around every launch
     stage_ms = {k: 0.0 for k in Engine.STAGES}
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         eng.profile(True)
         acc = []
         for _ in range(args.profile_steps):
@@ -459,27 +499,29 @@ def main():
 
     # parity of the last step on this rank's shard: every verdict, rule id and
     # consumed length against the oracle (test infrastructure, run after timing)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import refpy  # parity oracle: the checker and the CPU baseline, never the product path
-    cinfo = cpu_info()
-    threads = args.cpu_threads or cinfo["usable_cores"]  # every core of the process's CPU share
-    verdict = d_v.cpu().numpy()
-    rule = d_r.cpu().numpy()
-    consumed = d_c.cpu().numpy().view(np.uint32)
-    pol = refpy.Policy(full.policy)
-    t1 = time.perf_counter()
-    rv, rr, rc = pol.classify(w.conns, w.arena, w.offsets, w.lengths, w.conn_ids, threads)
-    cpu_all_s = time.perf_counter() - t1
-    mism = 0
-    for j in range(tiles):
-        sl = slice(j * nu, (j + 1) * nu)
-        mism += int(((verdict[sl] != rv) | (rule[sl] != rr) | (consumed[sl] != rc)).sum())
-    if mism:
-        log(f"[rank {rank}] PARITY FAILURE: {mism} of {n} requests differ from the oracle")
+    mism, hist = 0, None
+    if args.full:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import refpy  # parity oracle: the checker and the CPU baseline, never the product path
+        cinfo = cpu_info()
+        threads = args.cpu_threads or cinfo["usable_cores"]  # every core of the process's CPU share
+        verdict = d_v.cpu().numpy()
+        rule = d_r.cpu().numpy()
+        consumed = d_c.cpu().numpy().view(np.uint32)
+        pol = refpy.Policy(full.policy)
+        t1 = time.perf_counter()
+        rv, rr, rc = pol.classify(w.conns, w.arena, w.offsets, w.lengths, w.conn_ids, threads)
+        cpu_all_s = time.perf_counter() - t1
+        for j in range(tiles):
+            sl = slice(j * nu, (j + 1) * nu)
+            mism += int(((verdict[sl] != rv) | (rule[sl] != rr) | (consumed[sl] != rc)).sum())
+        if mism:
+            log(f"[rank {rank}] PARITY FAILURE: {mism} of {n} requests differ from the oracle")
+        hist = np.bincount(verdict, minlength=5)
 
     # e2e: host arena in pinned memory, PCIe both ways, chunked on two streams
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         t_e2e, moved, eout = e2e_pipeline(torch, eng, w, dev)
         e2e_mism = int(((eout[0] != rv) | (eout[1] != rr) | (eout[2] != rc)).sum())
         e2e = {"s": t_e2e, "requests": nu, "bytes": moved, "mismatches": e2e_mism}
@@ -506,7 +548,7 @@ def main():
     # CPU baseline (rank 0 at N = 1): the parity run above on every usable
     # core, plus one core on a bounded sample
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         m1 = min(nu, 300_000)
         sub = w.subset(np.arange(m1))
         t2 = time.perf_counter()
@@ -522,10 +564,10 @@ def main():
                "cgroup_cpu_quota": cinfo["cgroup_cpu_quota"], "cpu_model": cinfo["model"]}
 
     latency = None
-    if rank == 0 and world == 1 and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and not args.no_latency:
         latency = latency_leg(gen, refpy)
     streams = None
-    if rank == 0 and world == 1 and not args.no_streams:
+    if args.full and rank == 0 and world == 1 and not args.no_streams:
         try:
             streams = streams_leg(torch, eng, gen, refpy, w, dev, threads)
         except Exception as e:  # the streams leg never fails the bench line
@@ -571,7 +613,6 @@ def main():
     else:
         roofline = None
     step_gbps = step_alg / (kernel_ms / 1e3) / 1e9
-    hist = np.bincount(verdict, minlength=5)
     tot = totals.cpu().numpy()
     line = {
         "metric": METRIC,
@@ -580,6 +621,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak",
@@ -615,9 +657,10 @@ def main():
             "mismatches": e2e["mismatches"],
             "mode": "unique shard per GPU from pinned host memory: H2D arena + metadata, classify, D2H verdicts; "
                     "8 chunks alternating over 2 streams"},
-        "parity": {"checked": checked, "mismatches": mism, "bit_exact": mism == 0,
-                   "scope": "every request of the last step on every rank vs the oracle"},
-        "verdict_hist_last_step_rank0": hist.tolist(),
+        "parity": None if not args.full else {
+            "checked": checked, "mismatches": mism, "bit_exact": mism == 0,
+            "scope": "every request of the last step on every rank vs the oracle"},
+        "verdict_hist_last_step_rank0": None if hist is None else hist.tolist(),
         "counter_totals": {"allow_hits": int(tot[:nrules].sum()), "verdicts": tot[nrules:nrules + 5].tolist()},
     }
     print(json.dumps(line), flush=True)

@@ -33,7 +33,7 @@ def test_bench_two_ranks_one_device():
     cmd = [sys.executable, "-u", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cfg5", "--requests", "2000000",
-           "--unique", "100000", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-e2e",
+           "--unique", "100000", "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--no-e2e",
            "--no-latency", "--no-streams", "--profile-steps", "1", "--cpu-threads", "4"]
     env = dict(os.environ, L7G_DIST_BACKEND="gloo", L7G_DIST_ONE_DEVICE="1", OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd=ROOT)

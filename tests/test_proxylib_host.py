@@ -41,14 +41,15 @@ def test_no_gpu_no_module(monkeypatch):
 
 @pytest.mark.parametrize("proto,dst,exp", [
     ("memcache", "2.2.2.2:80", P.OK),
-    ("memcache", "[::1]:11211", P.OK),
+    # explicit ids: "::" in a generated id reads as pytest's node-id separator
+    pytest.param("memcache", "[::1]:11211", P.OK, id="memcache-v6-bracketed-ok"),
     ("http", "2.2.2.2:80", P.OK),
     ("kafka", "2.2.2.2:9092", P.OK),
     ("cassandra-not-here", "2.2.2.2:80", P.UNKNOWN_PARSER),
     ("memcache", "2.2.2.2", P.INVALID_ADDRESS),
     ("memcache", "2.2.2.2:0", P.INVALID_ADDRESS),
     ("memcache", "2.2.2.2:http", P.INVALID_ADDRESS),
-    ("memcache", "::1:80", P.INVALID_ADDRESS),
+    pytest.param("memcache", "::1:80", P.INVALID_ADDRESS, id="memcache-v6-unbracketed-invalid"),
     ("memcache", "2.2.2.2:4294967296", P.INVALID_ADDRESS),
 ])
 def test_on_new_connection(host_module, proto, dst, exp):

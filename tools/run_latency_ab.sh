@@ -13,7 +13,7 @@ grep -v amdgpu.ids $O/lat_timing.log
 for r in 1 2; do
 for v in prod old; do
   if [ $v = prod ]; then LP=""; else LP="$PWD/$O/oldlib"; fi
-  LD_LIBRARY_PATH=$LP${LD_LIBRARY_PATH:+:$LD_LIBRARY_PATH} timeout -k 10 300 python -u bench.py --workload cfg2 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-streams > $O/lat_${v}_$r.log 2>&1 || { tail -5 $O/lat_${v}_$r.log; exit 3; }
+  LD_LIBRARY_PATH=$LP${LD_LIBRARY_PATH:+:$LD_LIBRARY_PATH} timeout -k 10 300 python -u bench.py --workload cfg2 --steps 2 --warmup 1 --full --no-cpu-baseline --no-e2e --no-streams > $O/lat_${v}_$r.log 2>&1 || { tail -5 $O/lat_${v}_$r.log; exit 3; }
   grep '^{' $O/lat_${v}_$r.log > $O/lat_${v}_$r.json
   python3 -c "import json; d=json.load(open('$O/lat_${v}_$r.json'))['latency']; print('$v $r', d['sync_classify_host'], d['proxylib_ondata_memcached'])"
 done
