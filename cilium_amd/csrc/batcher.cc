@@ -43,6 +43,7 @@
 
 #include "../../include/l7gpu.h"
 #include "capi_internal.h"
+#include "kernels/call_layout.h"
 
 namespace {
 
@@ -311,8 +312,9 @@ l7g_batcher *l7g_batcher_create(l7g_engine *e, uint32_t max_requests, uint32_t m
     b->max_wait = std::chrono::microseconds(max_wait_us);
     const uint32_t cap_n = (std::max<uint32_t>(2 * b->max_n, kMinSlotRequests) + kLanes - 1) / kLanes * kLanes;
     const uint64_t cap_bytes = (uint64_t)cap_n * kSlotBytesPerRequest;
-    const size_t meta = ((size_t)cap_n * 16 + 255) & ~(size_t)255;
-    const size_t total = meta + cap_bytes + 64;  // (+64: aligned 16-byte reads past the last request stay inside)
+    // a slot: the inputs' layout with arrays of cap_n entries (kernels/call_layout.h; l7g_host_run_pinned's stride)
+    const size_t meta = l7::CallArenaOff(cap_n);
+    const size_t total = l7::CallInCap(cap_n, cap_bytes);
     for (auto &s : b->slots) {
         s.mem = (uint8_t *)l7g_pinned_alloc(total);
         s.pinned = s.mem != nullptr;
@@ -326,8 +328,8 @@ l7g_batcher *l7g_batcher_create(l7g_engine *e, uint32_t max_requests, uint32_t m
             return nullptr;
         }
         s.off = (uint64_t *)s.mem;
-        s.len = (uint32_t *)(s.mem + (size_t)cap_n * 8);
-        s.conn = (uint32_t *)(s.mem + (size_t)cap_n * 12);
+        s.len = (uint32_t *)(s.mem + l7::CallLenOff(cap_n));
+        s.conn = (uint32_t *)(s.mem + l7::CallConnOff(cap_n));
         s.arena = s.mem + meta;
         s.ready.reset(new std::atomic<uint8_t>[cap_n]);
         for (uint32_t k = 0; k < cap_n; k++) s.ready[k].store(EMPTY, std::memory_order_relaxed);

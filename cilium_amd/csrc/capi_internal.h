@@ -1,5 +1,6 @@
-// Library-internal entry points shared by the C-ABI (capi.cc) and the
-// proxylib shim (proxylib/shim.cc); not part of include/l7gpu.h.
+// Library-internal entry points shared by the C-ABI (capi.cc, host_call.cc),
+// the batcher (batcher.cc) and the proxylib shim (proxylib/shim.cc); not part
+// of include/l7gpu.h.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -24,8 +25,8 @@ int l7g_host_stage(l7g_engine *e, uint32_t n, uint64_t arena_len, uint8_t **aren
 int l7g_host_run(l7g_engine *e, uint32_t n, uint64_t arena_len, uint8_t *verdict, int32_t *rule, uint32_t *consumed);
 // The same with inputs already in pinned host memory (hipHostMalloc: a
 // batcher slot filled in place by its submitters): off[0..n), then len and
-// conn `stride` entries further on (len = (u8 *)off + stride * 8, conn =
-// (u8 *)off + stride * 12; stride >= n), and the request bytes as nseg
+// conn `stride` entries further on (kernels/call_layout.h: at CallLenOff(stride)
+// and CallConnOff(stride) bytes from off; stride >= n), and the request bytes as nseg
 // blocks that the device sees concatenated (off[] indexes the concatenation);
 // a block is `rows` rows of `width` bytes, `pitch` bytes apart in host memory
 // (one 2-D copy).  Copied to the device (or, one single-row block and a small

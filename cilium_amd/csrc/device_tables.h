@@ -3,6 +3,7 @@
 // out in one contiguous "table blob" per policy version; the kernels receive
 // typed pointers into it through HttpTables / KafkaTables (kernel arguments).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -24,6 +25,19 @@ enum : uint8_t { PROTO_NONE = 0, PROTO_HTTP = 1, PROTO_KAFKA = 2, PROTO_MEMCACHE
 #ifndef L7_KAFKA_CLASSES
 #define L7_KAFKA_CLASSES 8
 #endif
+
+// The counts block of the protocol split (kernels/partition.hip fills the list counts; the launch
+// plan, classify.cc, zeroes the block and hands its words to the classifiers): kCntWords u32 in front
+// of the index lists, [0, L7_KAFKA_CLASSES) the Kafka classes' counts, then the words named here.
+constexpr int kCntWords = 32;
+constexpr int kCntMc = L7_KAFKA_CLASSES;           // memcached retrievals (binary: the next word)
+constexpr int kCntHttp = L7_KAFKA_CLASSES + 2;     // HTTP
+constexpr int kCntMcText2 = L7_KAFKA_CLASSES + 3;  // memcached text commands other than retrievals
+constexpr int kCntKafkaWork = 26;                  // the Kafka kernel's entry counter
+constexpr int kCntHttpTiles = 28;                  // and the next word: HTTP tile counters (hot, general launch)
+constexpr int kCntKafkaZ = 31;                     // Kafka requests with compressed messages
+// the index lists behind the block, in words: L7_KAFKA_CLASSES x n Kafka, n memcached, n HTTP, n compressed Kafka
+constexpr size_t PartitionListWords(size_t n) { return (L7_KAFKA_CLASSES + 3) * n; }
 
 // Header slots recorded by the HTTP framer.
 enum : int { SLOT_METHOD = 0, SLOT_PATH = 1, SLOT_AUTHORITY = 2, SLOT_CUSTOM0 = 3 };

@@ -1,0 +1,277 @@
+// l7g_classify_host's per-thread path (product code), in three steps: stage,
+// fill, run (the batcher's flushers fill the staging in place and skip the
+// copy).  The staging's layout is kernels/call_layout.h.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "engine_state.h"
+
+// grow-only staging for the inputs and the outputs of a call
+static hipError_t HostGrow(HostCtx *H, uint32_t n, uint64_t arena_len) {
+    const size_t need_in = CallInCap(n, arena_len);
+    const size_t need_out = CallOutCap(n);
+    if (need_in <= H->in_cap && need_out <= H->out_cap) return hipSuccess;
+    // (the previous call of this thread has its answers; its kernels may still be
+    // retiring after storing the done word)
+    if (H->s) hipStreamSynchronize(H->s);
+    if (H->dev) hipFree(H->dev);
+    if (H->pin_in) hipHostFree(H->pin_in);
+    if (H->pin_out) hipHostFree(H->pin_out);
+    H->dev = H->pin_in = H->pin_out = H->pin_in_dev = H->pin_out_dev = nullptr;
+    H->in_cap = std::max(need_in + need_in / 4, (size_t)1 << 16);  // (some slack: batches vary)
+    H->out_cap = std::max(need_out + need_out / 4, (size_t)1 << 14);
+    hipError_t rc;
+    if ((rc = hipMalloc(&H->dev, H->in_cap + H->out_cap)) != hipSuccess) { H->in_cap = H->out_cap = 0; return rc; }
+    if ((rc = hipHostMalloc(&H->pin_in, H->in_cap, hipHostMallocDefault)) != hipSuccess ||
+        (rc = hipHostMalloc(&H->pin_out, H->out_cap, hipHostMallocDefault)) != hipSuccess ||
+        (rc = hipHostGetDevicePointer((void **)&H->pin_in_dev, H->pin_in, 0)) != hipSuccess ||
+        (rc = hipHostGetDevicePointer((void **)&H->pin_out_dev, H->pin_out, 0)) != hipSuccess) {
+        H->in_cap = H->out_cap = 0;
+        return rc;
+    }
+    if (!H->pin_done) {
+        if ((rc = hipHostMalloc((void **)&H->pin_done, 64, hipHostMallocDefault)) != hipSuccess) return rc;
+        *(volatile uint32_t *)H->pin_done = 0;
+        H->seq = 0;
+        if ((rc = hipHostGetDevicePointer((void **)&H->pin_done_dev, H->pin_done, 0)) != hipSuccess) return rc;
+    }
+    return hipSuccess;
+}
+
+// The calling thread's stream and staging on the engine's device (the engine
+// lock is held only while l7g_classify enqueues, so threads' copies and
+// kernels overlap); grow: the staging sized for n requests over arena_len bytes.
+static hipError_t HostEnter(l7g_engine *e, HostCtx **H, bool grow = false, uint32_t n = 0, uint64_t arena_len = 0) {
+    if (e->device < 0) return hipErrorNoDevice;
+    hipError_t rc = hipSetDevice(e->device);
+    if (rc != hipSuccess) return rc;
+    {
+        std::lock_guard<std::mutex> g(e->hmu);
+        auto &slot = e->hctx[std::this_thread::get_id()];
+        if (!slot) {
+            auto h = std::make_unique<HostCtx>();
+            if ((rc = hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking)) != hipSuccess) return rc;
+            slot = std::move(h);
+        }
+        *H = slot.get();
+    }
+    return grow ? HostGrow(*H, n, arena_len) : hipSuccess;
+}
+
+// classify a call whose inputs are in pinned host memory, wait for it, copy
+// the answers out
+static hipError_t HostRun(l7g_engine *e, HostCtx *H, uint32_t n, uint64_t arena_len, const HostIn &in,
+                          uint8_t *verdict, int32_t *rule, uint32_t *consumed, bool try_service = true) {
+    hipError_t rc = hipSuccess;
+    if (try_service && ServiceTry(e, n, arena_len, in, verdict, rule, consumed, &rc)) return rc;
+    const size_t nn = CallNn(n);
+    const size_t a_off = CallArenaOff(nn);
+    // A small call (the Envoy adapter's Allowed(), one OnData, a light batch)
+    // is latency, not bandwidth: the kernels read the inputs from and write the
+    // verdicts to the pinned memory in place (zero-copy, over PCIe), so the
+    // call is one launch and a wait instead of copy, launch, copy, wait.
+    static const bool zc_on = [] {
+        const char *v = getenv("L7G_SYNC_ZEROCOPY");
+        return !(v && v[0] == '0');
+    }();
+    const bool zc = zc_on && (in.nseg == 0 || (in.nseg == 1 && in.seg[0].rows <= 1)) && n <= kZeroCopyMaxRequests &&
+                    a_off + arena_len <= kZeroCopyMaxBytes;
+    hipStream_t s = H->s;
+    const uint64_t *d_o;
+    const uint32_t *d_l, *d_c;
+    const uint8_t *d_a;
+    uint8_t *d_out = H->dev + H->in_cap;
+    CopyIn pre{};  // zero-copy: the inputs' copy into HBM, done by the call's first kernel
+    if (zc) {
+        // The inputs are copied into HBM (one PCIe round trip per 64 KiB, every
+        // load in flight before the first store: by the call's first kernel when
+        // it is one workgroup, else by copy_in_kernel) and classified there: read
+        // in place, every dependent read of a framer was a PCIe round trip.  The
+        // verdicts are still written to the pinned memory in place.
+        d_out = H->pin_out_dev;
+        uint8_t *d_in = H->dev;
+        CopyIn ci{};
+        const size_t a_at = in.nseg ? (size_t)((const uint8_t *)in.seg[0].p - H->pin_in) : 0;
+        if (in.off == (const uint64_t *)H->pin_in && in.len == (const uint32_t *)(H->pin_in + CallLenOff(nn)) &&
+            in.conn == (const uint32_t *)(H->pin_in + CallConnOff(nn)) && a_at <= a_off && a_at % 16 == 0) {
+            // the thread's staging (packed): one piece
+            ci.p[0] = {H->pin_in_dev, d_in, (uint64_t)CallInBytes(nn, arena_len)};
+            ci.n = 1;
+            d_o = (const uint64_t *)d_in;
+            d_l = (const uint32_t *)(d_in + CallLenOff(nn));
+            d_c = (const uint32_t *)(d_in + CallConnOff(nn));
+            d_a = d_in + a_at;
+        } else {
+            // a batcher slot: four pieces into [off | len | conn | arena], the arrays
+            // nn4 entries long so each starts 16-byte aligned (call_layout.h)
+            void *dp = nullptr;
+            auto dev_ptr = [&](const void *h) -> const uint8_t * {
+                if (rc == hipSuccess) rc = hipHostGetDevicePointer(&dp, const_cast<void *>(h), 0);
+                return (const uint8_t *)dp;
+            };
+            const uint8_t *h_o = dev_ptr(in.off), *h_l = dev_ptr(in.len), *h_c = dev_ptr(in.conn);
+            const uint8_t *h_a = in.nseg ? dev_ptr(in.seg[0].p) : h_o;
+            if (rc != hipSuccess) return rc;
+            auto al16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
+            if (!(al16(h_o) && al16(h_l) && al16(h_c) && al16(h_a))) return hipErrorInvalidValue;  // (slots are)
+            const size_t nn4 = CallNn4(n);
+            ci.p[0] = {h_o, d_in, (uint64_t)nn * 8};
+            ci.p[1] = {h_l, d_in + CallLenOff(nn4), (uint64_t)nn * 4};
+            ci.p[2] = {h_c, d_in + CallConnOff(nn4), (uint64_t)nn * 4};
+            ci.p[3] = {h_a, d_in + a_off, in.nseg ? arena_len : 0};
+            ci.n = 4;
+            d_o = (const uint64_t *)d_in;
+            d_l = (const uint32_t *)(d_in + CallLenOff(nn4));
+            d_c = (const uint32_t *)(d_in + CallConnOff(nn4));
+            d_a = in.nseg ? d_in + a_off : d_in;
+        }
+        pre = ci;
+        pre.done = H->pin_done_dev;
+        pre.seq = NextSeq(H->seq);
+    } else {
+        uint8_t *d_in = H->dev;
+        const bool staging = in.off == (const uint64_t *)H->pin_in;
+        const size_t st = staging ? nn : in.stride ? in.stride : nn;
+        d_o = (const uint64_t *)d_in;
+        d_l = (const uint32_t *)(d_in + CallLenOff(st));
+        d_c = (const uint32_t *)(d_in + CallConnOff(st));
+        d_a = d_in + CallArenaOff((uint32_t)st);
+        if (staging) {  // the thread's staging: one copy of the whole layout
+            rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, s);
+        } else {
+            if (in.stride) {  // the three arrays in one copy
+                rc = hipMemcpyAsync(d_in, in.off, CallConnOff(st) + (size_t)n * 4, hipMemcpyHostToDevice, s);
+            } else {
+                rc = hipMemcpyAsync((void *)d_o, in.off, (size_t)n * 8, hipMemcpyHostToDevice, s);
+                if (rc == hipSuccess) rc = hipMemcpyAsync((void *)d_l, in.len, (size_t)n * 4, hipMemcpyHostToDevice, s);
+                if (rc == hipSuccess) rc = hipMemcpyAsync((void *)d_c, in.conn, (size_t)n * 4, hipMemcpyHostToDevice, s);
+            }
+            uint64_t at = 0;
+            for (int k = 0; k < in.nseg && rc == hipSuccess; k++) {
+                const l7g_host_seg &g = in.seg[k];
+                if (!g.width || !g.rows) continue;
+                if (g.rows == 1)
+                    rc = hipMemcpyAsync((void *)(d_a + at), g.p, g.width, hipMemcpyHostToDevice, s);
+                else
+                    rc = hipMemcpy2DAsync((void *)(d_a + at), g.width, g.p, g.pitch, g.width, g.rows,
+                                          hipMemcpyHostToDevice, s);
+                at += g.width * g.rows;
+            }
+        }
+    }
+    uint8_t *d_v = d_out;
+    int32_t *d_r = (int32_t *)(d_out + CallRuleOff(n));
+    uint32_t *d_cons = (uint32_t *)(d_out + CallConsumedOff(n));
+    bool signaled = false;
+    if (rc == hipSuccess)
+        rc = (hipError_t)Classify(e, d_a, arena_len, d_o, d_l, d_c, n, d_v, d_r, d_cons, nullptr, s, in.conn,
+                                  pre.n ? &pre : nullptr, &signaled);
+    if (rc == hipSuccess && n && !zc)
+        rc = hipMemcpyAsync(H->pin_out, d_out, CallOutBytes(n), hipMemcpyDeviceToHost, s);
+    // One workgroup answered the call: its done word says the answers are in
+    // pinned memory (a spin on that word is some microseconds shorter than the
+    // stream's completion signal); past 2 ms, or otherwise, wait on the stream,
+    // which also reports a kernel's failure.
+    bool done = false;
+    if (rc == hipSuccess && signaled) {
+        done = SpinUntil([&] { return *(volatile uint32_t *)H->pin_done; }, pre.seq, std::chrono::milliseconds(2));
+        std::atomic_thread_fence(std::memory_order_acquire);
+    }
+    if (rc == hipSuccess && !done) rc = hipStreamSynchronize(s);
+    if (rc == hipSuccess && n) {
+        const uint8_t *po = H->pin_out;
+        memcpy(verdict, po, n);
+        memcpy(rule, po + CallRuleOff(n), (size_t)n * 4);
+        memcpy(consumed, po + CallConsumedOff(n), (size_t)n * 4);
+    }
+    return rc;
+}
+
+int l7g_host_stage(l7g_engine *e, uint32_t n, uint64_t arena_len, uint8_t **arena, uint64_t **off, uint32_t **len,
+                   uint32_t **conn) {
+    HostCtx *H = nullptr;
+    const hipError_t rc = HostEnter(e, &H, true, n, arena_len);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t nn = CallNn(n);
+    *off = (uint64_t *)H->pin_in;
+    *len = (uint32_t *)(H->pin_in + CallLenOff(nn));
+    *conn = (uint32_t *)(H->pin_in + CallConnOff(nn));
+    *arena = H->pin_in + CallArenaOff(nn);
+    return 0;
+}
+
+static int HostRunStaged(l7g_engine *e, uint32_t n, uint64_t arena_len, uint8_t *verdict, int32_t *rule,
+                         uint32_t *consumed, bool try_service) {
+    HostCtx *H = nullptr;
+    hipError_t rc = HostEnter(e, &H);
+    if (rc == hipSuccess) {
+        const size_t nn = CallNn(n);
+        const l7g_host_seg seg{H->pin_in + CallArenaOff(nn), arena_len, arena_len, 1};
+        const HostIn in{(const uint64_t *)H->pin_in, (const uint32_t *)(H->pin_in + CallLenOff(nn)),
+                        (const uint32_t *)(H->pin_in + CallConnOff(nn)), nn, &seg, 1};
+        rc = HostRun(e, H, n, arena_len, in, verdict, rule, consumed, try_service);
+    }
+    return (int)rc;
+}
+
+int l7g_host_run(l7g_engine *e, uint32_t n, uint64_t arena_len, uint8_t *verdict, int32_t *rule, uint32_t *consumed) {
+    return HostRunStaged(e, n, arena_len, verdict, rule, consumed, true);
+}
+int l7g_host_run_pinned(l7g_engine *e, uint32_t n, const uint64_t *off, size_t stride, const l7g_host_seg *seg,
+                        int nseg, uint8_t *verdict, int32_t *rule, uint32_t *consumed) {
+    HostCtx *H = nullptr;
+    uint64_t arena_len = 0;
+    for (int k = 0; k < nseg; k++) arena_len += seg[k].width * seg[k].rows;
+    const uint32_t st = (uint32_t)std::max<size_t>(stride, n);
+    // device staging for `st` entries' arrays and the arena, pinned outputs for n
+    hipError_t rc = HostEnter(e, &H, true, st, arena_len);
+    if (rc == hipSuccess) {
+        const uint8_t *b = (const uint8_t *)off;
+        const HostIn in{off, (const uint32_t *)(b + CallLenOff(stride)), (const uint32_t *)(b + CallConnOff(stride)),
+                        stride, seg, nseg};
+        rc = HostRun(e, H, n, arena_len, in, verdict, rule, consumed);
+    }
+    return (int)rc;
+}
+
+int l7g_host_reserve(l7g_engine *e, uint32_t n, uint64_t arena_len) {
+    HostCtx *H = nullptr;
+    return (int)HostEnter(e, &H, true, n, arena_len);
+}
+
+int l7g_engine_has_device(const l7g_engine *e) { return e && e->device >= 0 ? 1 : 0; }
+
+void *l7g_pinned_alloc(size_t bytes) {
+    void *p = nullptr;
+    return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+}
+void l7g_pinned_free(void *p) {
+    if (p) hipHostFree(p);
+}
+
+extern "C" {
+
+int l7g_classify_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                      const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed) {
+    {  // a call a service takes goes from the caller's buffers straight into the service's staging
+        const l7g_host_seg seg{arena, arena_len, arena_len, 1};
+        const HostIn in{off, len, conn, 0, &seg, 1};
+        hipError_t rc = hipSuccess;
+        if (e->device >= 0 && ServiceTry(e, n, arena_len, in, verdict, rule, consumed, &rc)) return (int)rc;
+    }
+    uint8_t *pa;
+    uint64_t *po;
+    uint32_t *pl, *pc;
+    int rc = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
+    if (rc != 0) return rc;
+    if (n) {
+        memcpy(po, off, (size_t)n * 8);
+        memcpy(pl, len, (size_t)n * 4);
+        memcpy(pc, conn, (size_t)n * 4);
+    }
+    if (arena_len) memcpy(pa, arena, arena_len);
+    return HostRunStaged(e, n, arena_len, verdict, rule, consumed, false);
+}
+
+}  // extern "C"

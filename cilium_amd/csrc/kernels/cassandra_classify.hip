@@ -32,6 +32,7 @@
 
 #include "../device_tables.h"
 #include "cass_parse.h"
+#include "launch.h"
 
 namespace l7 {
 

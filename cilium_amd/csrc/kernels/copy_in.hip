@@ -14,6 +14,7 @@
 
 #include "copy_in_types.h"
 #include "gmem.h"
+#include "launch.h"
 
 namespace l7 {
 

@@ -1,5 +1,5 @@
 // A small call's input pieces, copied from pinned host memory into HBM before
-// the classifiers read them (capi.cc HostRun; kernels/copy_in.hip, or the
+// the classifiers read them (host_call.cc HostRun; kernels/copy_in.hip, or the
 // first kernel of the call when it runs as one workgroup).  Plain types: the
 // host side includes this too.
 #pragma once

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "../device_tables.h"
+#include "launch.h"
 
 namespace l7 {
 

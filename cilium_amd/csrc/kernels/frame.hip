@@ -23,6 +23,7 @@
 
 #include "../device_tables.h"
 #include "gmem.h"
+#include "launch.h"
 
 namespace l7 {
 

@@ -47,6 +47,7 @@
 #include "../device_tables.h"
 #include "copy_in.h"
 #include "gmem.h"
+#include "launch.h"
 #include "service.h"
 
 // OCKL's DPP wave reductions (64-bit forms are not declared by hip_runtime.h)

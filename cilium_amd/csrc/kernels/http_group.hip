@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../device_tables.h"
+#include "launch.h"
 
 namespace l7 {
 

@@ -16,6 +16,7 @@
 
 #include "../device_tables.h"
 #include "../regex/nfa_walk.h"
+#include "launch.h"
 
 namespace l7 {
 

@@ -28,6 +28,7 @@
 
 #include "../device_tables.h"
 #include "kafka_dec.h"
+#include "launch.h"
 
 namespace l7 {
 

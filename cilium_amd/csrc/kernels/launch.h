@@ -1,0 +1,57 @@
+// Host entry points of the kernels (product code): every launcher, scratch
+// size and phase-time reader the C-ABI's host files call.  The .hip file that
+// defines one includes this header too, so the compiler checks the two.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include "../device_tables.h"
+#include "copy_in_types.h"
+#include "service_types.h"
+
+namespace l7 {
+
+hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const uint32_t *sel, const uint32_t *sel_count,
+                              bool any_cold, bool answer_other, uint32_t *tile_ctr, bool latency, const CopyIn *ci,
+                              hipStream_t stream);
+hipError_t LaunchKafkaClassify(const Batch &B, const KafkaTables &T, const uint32_t *sel, const uint32_t *sel_count,
+                               bool answer_other, uint32_t *zlist, uint32_t *zcount, uint32_t *work,
+                               hipStream_t stream, int leave_per_cu = 0);
+hipError_t LaunchKafkaInflate(const Batch &B, const uint32_t *zlist, const uint32_t *zcount, uint8_t *region,
+                              hipStream_t stream);
+uint32_t KafkaInflateBlocks();
+uint32_t KafkaInflateRegionBytes();
+hipError_t LaunchMemcacheClassify(const Batch &B, const McTables &T, const uint32_t *sel, const uint32_t *sel2,
+                                  const uint32_t *sel_count, bool answer_other, uint32_t scratch_lanes,
+                                  hipStream_t stream, const CopyIn *ci = nullptr);
+hipError_t LaunchR2d2Classify(const Batch &B, const R2Tables &T, bool answer_other, uint32_t scratch_lanes,
+                              hipStream_t stream);
+size_t CassandraScratchBytes(uint32_t n);
+hipError_t LaunchCassandraClassify(const Batch &B, const CassTables &T, void *scratch, size_t scratch_bytes,
+                                   bool answer_other, uint32_t nfa_lanes, hipStream_t stream);
+hipError_t LaunchCounters(const uint8_t *verdict, const int32_t *rule, uint32_t n, uint32_t nrules,
+                          uint64_t *counters, uint32_t *scratch, hipStream_t stream);
+size_t CountersScratchBytes();
+hipError_t LaunchFlowStats(const Batch &B, uint32_t nkeys, uint64_t *acc, hipStream_t stream);
+uint32_t FlowStatsMaxKeys();
+hipError_t LaunchHttpNfa(const Batch &B, const HttpTables &T, uint32_t scratch_lanes, hipStream_t stream);
+hipError_t LaunchPartition(const Batch &B, uint32_t *sel_kafka, uint32_t *sel_mc, uint32_t *sel_http, uint32_t *counts,
+                           hipStream_t stream);
+hipError_t LaunchFrameStreams(const uint8_t *arena, uint64_t arena_len, const uint64_t *s_off, const uint32_t *s_len,
+                              const uint32_t *s_conn, uint32_t n, const DevConn *conns, uint32_t nconns,
+                              uint32_t max_frames, uint64_t *frame_off, uint32_t *frame_len, uint32_t *conn_out,
+                              uint32_t *nframes, hipStream_t stream);
+hipError_t HttpPhaseTimes(uint64_t *out, bool reset);
+hipError_t KafkaPhaseTimes(uint64_t *out, bool reset);
+hipError_t LaunchCopyIn(const CopyIn &c, hipStream_t stream);
+hipError_t FramePhaseTimes(uint64_t *out, bool reset);
+hipError_t LaunchHttpGroup(const Batch &B, const HttpTables &T, const uint32_t *sel, const uint32_t *sel_count,
+                           uint32_t n, bool answer_other, uint32_t *ctl, uint32_t *hist, uint32_t *cursor,
+                           uint32_t *segs, uint32_t *gsel, uint32_t *gbig, hipStream_t stream);
+hipError_t LaunchHttpGrouped(const Batch &B, const HttpTables &T, const uint32_t *gsel, const uint32_t *segs,
+                             const uint32_t *gbig, uint32_t *ctl, bool any_big, hipStream_t stream);
+hipError_t LaunchHttpService(SvcBox *box, const SvcStatic &S, const HttpTables &T, uint32_t seen0, uint64_t idle,
+                             hipStream_t stream);
+hipError_t LaunchMemcacheService(SvcBox *box, const SvcStatic &S, const McTables &T, uint32_t seen0, uint64_t idle,
+                                 hipStream_t stream);
+
+}  // namespace l7

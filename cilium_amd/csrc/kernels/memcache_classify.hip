@@ -28,6 +28,7 @@
 #include "../regex/nfa_walk.h"
 #include "copy_in.h"
 #include "gmem.h"
+#include "launch.h"
 #include "service.h"
 
 namespace l7 {

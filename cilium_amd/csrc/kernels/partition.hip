@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../device_tables.h"
+#include "launch.h"
 
 namespace l7 {
 
@@ -37,18 +38,19 @@ constexpr int kWaves = kBlock / 64;
 // list classes: 0..kKafkaClasses-1 Kafka by kind / length, then memcached
 // text, memcached binary, other memcached text, then HTTP by length
 // (kHttpSub classes, one list).  counts[] keeps one word per list: the Kafka
-// classes, memcached retrievals, memcached binary, HTTP, other memcached text.
+// classes, memcached retrievals, memcached binary, HTTP, other memcached text
+// (device_tables.h: kCntMc, kCntHttp, kCntMcText2).
 constexpr int kKafkaClasses = L7_KAFKA_CLASSES;
 constexpr int kMcText = kKafkaClasses, kMcBinary = kKafkaClasses + 1;
 constexpr int kMcText2 = kKafkaClasses + 2;  // text commands not starting with 'g' (storage, delete, ...)
 constexpr int kHttp0 = kKafkaClasses + 3;    // HTTP by length class: kHttp0 .. kHttp0 + kHttpSub - 1
 constexpr int kHttpSub = 4;  // (2 classes: cfg5 36.23 ms, 8: 36.25, 4: 36.06-36.16, none: 36.52-36.60)
 constexpr int kClasses = kHttp0 + kHttpSub;
-constexpr int kCntHttp = kKafkaClasses + 2, kCntMcText2 = kKafkaClasses + 3;  // their counts[] words
 __device__ __forceinline__ int count_word(int c) { return c < kMcText2 ? c : c == kMcText2 ? kCntMcText2 : kCntHttp; }
 
 static_assert(kKafkaClasses == 1 || kKafkaClasses == 8, "length classes");
-static_assert(kKafkaClasses + 4 <= 26, "counts[26..31] hold the work counters and the compressed-Kafka count");
+static_assert(kMcText == kCntMc && kCntMcText2 < kCntKafkaWork && kCntKafkaZ < kCntWords,
+              "the list counts end before the work counters and the compressed-Kafka count");
 // HTTP length classes: within a workgroup's 4096 requests the HTTP entries are
 // written class by class (stream order within a class), so an HTTP tile of 64
 // entries mostly holds requests of about one length, and the kernel's

@@ -1,5 +1,5 @@
 // The resident service kernels' mailbox loop (product code; the box layout is
-// service_types.h, the host side capi.cc Service).  One workgroup polls
+// service_types.h, the host side service.cc Service).  One workgroup polls
 // pinned host memory for the synchronous drop-in calls (one Allowed(), one
 // OnData), so such a call costs no launch and no completion signal: the host
 // writes the call's inputs and a sequence number, the workgroup copies the
@@ -80,21 +80,20 @@ __device__ __forceinline__ SvcCall svc_next(SvcBox *box, uint32_t &seen, uint64_
     return c;
 }
 
-// The call's Batch over the service's staging (layout: service_types.h).
+// The call's Batch over the service's staging (packed layout: call_layout.h).
 __device__ __forceinline__ Batch svc_batch(const SvcStatic &S, const SvcCall &c) {
-    const uint32_t nn = c.n ? c.n : 1;
-    const size_t a_off = SvcArenaOff(c.n);
+    const size_t nn = CallNn(c.n);
     Batch B;
-    B.arena = S.dev_in + a_off;
+    B.arena = S.dev_in + CallArenaOff(nn);
     B.arena_len = c.arena_len;
     B.offs = (const uint64_t *)S.dev_in;
-    B.lens = (const uint32_t *)(S.dev_in + (size_t)nn * 8);
-    B.conn_ids = (const uint32_t *)(S.dev_in + (size_t)nn * 12);
+    B.lens = (const uint32_t *)(S.dev_in + CallLenOff(nn));
+    B.conn_ids = (const uint32_t *)(S.dev_in + CallConnOff(nn));
     B.conns = S.conns;
     B.nconns = S.nconns;
     B.verdict = S.pin_out;
-    B.rule = (int32_t *)(S.pin_out + ((nn + 3) & ~3u));
-    B.consumed = (uint32_t *)(S.pin_out + ((nn + 3) & ~3u) + (size_t)nn * 4);
+    B.rule = (int32_t *)(S.pin_out + CallRuleOff(c.n));
+    B.consumed = (uint32_t *)(S.pin_out + CallConsumedOff(c.n));
     B.n = c.n;
     return B;
 }
@@ -103,7 +102,7 @@ __device__ __forceinline__ CopyIn svc_copy(const SvcStatic &S, SvcBox *box, cons
     CopyIn ci{};
     ci.p[0].src = S.pin_in;
     ci.p[0].dst = S.dev_in;
-    ci.p[0].bytes = SvcArenaOff(c.n) + c.arena_len;
+    ci.p[0].bytes = CallInBytes(CallNn(c.n), c.arena_len);
     ci.n = 1;
     ci.done = &box->done;
     ci.seq = c.seq;

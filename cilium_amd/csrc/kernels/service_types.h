@@ -1,4 +1,4 @@
-// The resident service kernels' mailbox (product code; capi.cc Service,
+// The resident service kernels' mailbox (product code; service.cc Service,
 // kernels http_service_kernel / memcache_service_kernel): a synchronous
 // drop-in call (one Allowed(), one OnData) is posted here instead of being
 // launched.  Plain types: the host side includes this too.  The box lives in
@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../device_tables.h"
+#include "call_layout.h"
 #include "copy_in_types.h"
 
 namespace l7 {
@@ -16,11 +17,10 @@ namespace l7 {
 enum : uint32_t { kSvcStopped = 0, kSvcRunning = 1, kSvcExiting = 2 };
 
 // The service's own staging (allocated with it; kernel arguments for its
-// lifetime): a call's inputs in the layout of l7g_classify_host's staging --
-// [off u64[nn] | len u32[nn] | conn u32[nn] | arena at a_off], nn = max(n, 1),
-// a_off = (16 nn + 255) & ~255 -- in pinned memory, copied by the kernel into
-// dev_in; its answers [verdict u8[(nn + 3) & ~3] | rule i32[nn] | consumed
-// u32[nn]] written to pinned memory in place.  conns / tables: the engine's
+// lifetime): a call's inputs in the packed layout of l7g_classify_host's
+// staging (call_layout.h) in pinned memory, copied by the kernel into dev_in;
+// its answers, in that header's output layout, written to pinned memory in
+// place.  conns / tables: the engine's
 // as they were when the kernel was launched (a policy or connection update
 // stops the service first).
 struct SvcStatic {
@@ -50,7 +50,5 @@ struct SvcBox {
     uint32_t pad[9];
 };
 static_assert(sizeof(SvcBox) == 64, "one line");
-
-L7_HD constexpr inline size_t SvcArenaOff(uint32_t n) { return ((size_t)(n ? n : 1) * 16 + 255) & ~(size_t)255; }
 
 }  // namespace l7

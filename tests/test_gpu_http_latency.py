@@ -1,7 +1,7 @@
 """The HTTP latency kernel (one request per wave, its header lines framed
 side by side; http_classify.hip:lat_request) against the oracle.
 
-Calls of at most 64 requests take it (capi.cc kLatencyMax): every workload
+Calls of at most 64 requests take it (engine_state.h kLatencyMax): every workload
 below is cut into calls of 1..64 requests and each answer must equal the
 oracle's -- the cfg1 / cfg2 streams, adversarial and chunked requests,
 many rule sets (hot and general instantiations), and header blocks around the

@@ -1,4 +1,4 @@
-"""The resident services (kernels/service.h, capi.cc Service): the
+"""The resident services (kernels/service.h, service.cc Service): the
 synchronous calls of l7g_classify_host whose requests are all HTTP (at most 8)
 or all memcached (at most 64) are posted to a polling workgroup instead of
 launched.  Their answers must be the launched path's and the oracle's, across

@@ -3,7 +3,7 @@ lists and work counters in use) on two caller streams, four calls in flight:
 every verdict, rule id and consumed length, and the per-rule counters, equal
 the oracle's -- calls in a row on one stream, and calls on two streams, do not
 see each other's lists or counters.  At this size the memcached kernel runs on
-the scratch set's side stream beside the Kafka kernel (capi.cc kBesideMin), so
+the scratch set's side stream beside the Kafka kernel (engine_state.h kBesideMin), so
 the test also covers that fork / join with two caller streams in flight."""
 import numpy as np
 import pytest

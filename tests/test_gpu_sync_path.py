@@ -3,7 +3,7 @@
 A call of at most kHostScanMax requests whose connections are all one
 parser's (one Allowed(), one OnData) launches only that parser's kernel,
 unpartitioned, behind a one-kernel copy of its inputs into HBM
-(capi.cc:Classify, HostRun).  Every subset below -- one protocol, one
+(classify.cc:Classify, host_call.cc:HostRun).  Every subset below -- one protocol, one
 protocol plus unknown and parserless connections, every protocol at once,
 a single request, zero-length requests -- must answer exactly as the oracle
 does, and a call must not see a previous call's answers."""

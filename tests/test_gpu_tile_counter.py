@@ -1,7 +1,7 @@
 """The HTTP kernels' tile counters across calls.
 
 A batch of at least 2^18 HTTP requests on an HTTP-only engine takes its
-tiles from a per-stream counter (capi.cc Classify).  Several such calls in a
+tiles from a per-stream counter (classify.cc Classify).  Several such calls in a
 row -- long requests (one tile per atomic), short ones (four per atomic),
 and a small call in between (fixed stride) -- must each answer every request
 exactly as the oracle does: a counter left non-zero would skip tiles."""
