@@ -334,7 +334,8 @@ int l7g_policy_update_proto(l7g_engine *e, const uint8_t *buf, size_t len, char 
 constexpr uint64_t kTablesMagic = 0x3154473754L;  // "T7G1"
 // format and struct-layout tag: an image from a build with another layout of
 // the device records is refused (it would be read at the wrong offsets)
-constexpr uint64_t kTablesAbi = 2ull << 56 | (uint64_t)sizeof(DevRuleset) << 48 | (uint64_t)sizeof(DevNfa) << 36 |
+// (3: HTTP images carry the null DFA behind their header, kImgNullDfaOff)
+constexpr uint64_t kTablesAbi = 3ull << 56 | (uint64_t)sizeof(DevRuleset) << 48 | (uint64_t)sizeof(DevNfa) << 36 |
                                 (uint64_t)sizeof(ImgHeader) << 24 | (uint64_t)sizeof(DevKafkaRuleset) << 12 |
                                 (uint64_t)sizeof(McImgHeader);
 

@@ -154,6 +154,13 @@ struct ImgHeader {         // 80 B, at offset 0 of every image
     uint32_t ntab_mul;     // multiplier of l7_name_hash, chosen so the names do not collide
 };
 static_assert(sizeof(ImgHeader) == 80, "ImgHeader layout");
+// The null DFA, right behind the header of every image: 256 zero bytes that
+// serve as the class table (every byte -> class 0) and as the one transition
+// row (state 0 -> state 0) of a slot no DFA constrains.  With it, and with
+// state 0 of every DFA a real row that loops back to itself, the framer's DFA
+// step needs neither a "has a DFA" nor a "state is dead" test.
+constexpr uint32_t kImgNullDfaOff = sizeof(ImgHeader);
+constexpr uint32_t kImgNullDfaBytes = 256;
 
 // Header-name table (the framer's one-probe shortcut for the name DFA): the
 // names of the name DFA that are at most 15 bytes of [0-9a-z-], lower-cased

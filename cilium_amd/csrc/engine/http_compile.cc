@@ -463,7 +463,7 @@ int HttpCompiler::Compile(const std::vector<const HttpRule *> &rules, uint8_t te
     }
 
     // ---- assemble the image
-    std::vector<uint8_t> img(sizeof(ImgHeader));
+    std::vector<uint8_t> img(kImgNullDfaOff + kImgNullDfaBytes);  // header, null DFA (zeros)
     std::vector<DevDfa> dd(built.size());
     H.dfa_off = Append(img, dd.data(), dd.size());
     H.init_off = Append(img, init.data(), init.size());
@@ -511,6 +511,9 @@ int HttpCompiler::Compile(const std::vector<const HttpRule *> &rules, uint8_t te
     }
     for (size_t k = 0; k < built.size(); k++) {
         const re::DFA &d = built[k].d;
+        // the kernel steps a dead walk like any other: row 0 must loop back
+        for (int c = 0; c < d.ncls; c++)
+            if (d.next[c] != 0) { *err = "DFA whose dead state is left again"; return -1; }
         dd[k].ncls = (uint16_t)d.ncls;
         dd[k].start = (uint16_t)d.start;
         dd[k].cls_off = Append(img, d.cls, 256);

@@ -120,8 +120,11 @@ __device__ __forceinline__ bool is_tchar(uint32_t c) {
     const uint32_t m2 = 0xC7FFFFFEu;  // 0x40-0x5F
     const uint32_t m3 = 0x57FFFFFFu;  // 0x60-0x7F
     const uint32_t w = c < 0x40 ? m1 : (c < 0x60 ? m2 : m3);
-    return (c - 0x20u < 0x60u) && ((w >> (c & 31)) & 1);
+    return (c - 0x20u < 0x60u) & ((w >> (c & 31)) & 1);
 }
+
+// a byte that ends a header value: a CTL other than HT, or DEL (branch-free)
+__device__ __forceinline__ bool value_stop(uint32_t c) { return ((c < 0x20) & (c != '\t')) | (c == 0x7F); }
 
 // Per-dword SWAR: bit 7 of byte i set iff byte i < 0x20 or == 0x7F (exact).
 __device__ __forceinline__ uint32_t stop_bits(uint32_t x) {
@@ -224,41 +227,59 @@ struct Lane {
     bool have_cl, chunked, cl_bad, cl_ws, in_ows;
     uint32_t ndig;      // Content-Length digits; Transfer-Encoding: bytes of "chunked" matched (0xFF: no)
     uint64_t clv, cl;   // clv: Content-Length value; in the chunked body: the chunk size
-    // DFA of the current slot (kDfasPerPass == 1); dtrans == 0: none
-    uint32_t dcls, dtrans, dmask, dncls, st, saved;
-    uint32_t dabs;      // states >= dabs (and 0) are absorbing
+    // DFA of the current slot (kDfasPerPass == 1).  A slot without one walks
+    // the image's null DFA (kImgNullDfaOff: class 0 for every byte, state 0
+    // looping), so a step needs no test; dmask == 0 marks it.
+    uint32_t dcls, dtrans, dmask, drow, st, saved;  // drow: bytes per transition row
+    uint32_t dabs1;     // st - 1 < dabs1: neither dead (0) nor absorbing (>= dabs1 + 1)
     uint64_t acc[kChunksPerPass];
     uint32_t cg, dg;    // chunk group, DFA group of this pass
 };
 static_assert(kDfasPerPass == 1, "one DFA per slot per framing pass");
 
+// No DFA on the lane's slot: the null DFA, dead from the start.
+__device__ __forceinline__ void null_dfa(Lane &L) {
+    L.st = 0;
+    L.dcls = L.dtrans = kImgNullDfaOff;
+    L.dmask = L.drow = 0;
+    L.dabs1 = ~0u;
+}
+
 template <bool kLds>
 __device__ __forceinline__ void slot_begin(const Img<kLds> &I, Lane &L, uint32_t slot) {
     const uint32_t lo = I.u8(offsetof(ImgHeader, slot_dfa) + slot) + L.dg;
     const uint32_t hi = I.u8(offsetof(ImgHeader, slot_dfa) + slot + 1);
-    L.st = 0;
-    L.dcls = L.dtrans = L.dmask = L.dncls = L.dabs = 0;
+    null_dfa(L);
     if (lo < hi) {
         const uint32_t d = HDR_U32(I, dfa_off) + lo * sizeof(DevDfa);
         L.dcls = I.u32(d + 0);
         L.dtrans = I.u32(d + 4);
         L.dmask = I.u32(d + 8);
         const uint32_t nc_st = I.u32(d + 12);
-        L.dncls = nc_st & 0xFFFF;
+        L.drow = 2 * (nc_st & 0xFFFF);
         L.st = nc_st >> 16;
-        L.dabs = I.u32(d + 16);
+        L.dabs1 = I.u32(d + 16) - 1;
     }
 }
 
+// One DFA step, branch-free: state 0 is a real row that loops back to itself
+// and every slot has a class table (the null DFA's when it has no DFA).  The
+// row address is a 24-bit multiply-add on the state (states and row sizes are
+// 16-bit): one instruction behind the state, the class term added beforehand.
+__device__ __forceinline__ uint32_t row_addr(uint32_t trans, uint32_t st, uint32_t row, uint32_t k) {
+    return __umul24(st, row) + (trans + 2 * k);
+}
 template <bool kLds>
 __device__ __forceinline__ void dfa_step(const Img<kLds> &I, Lane &L, uint32_t c) {
-    if (L.st) L.st = I.u16(L.dtrans + 2 * (L.st * L.dncls + I.u8(L.dcls + c)));
+    L.st = I.u16(row_addr(L.dtrans, L.st, L.drow, I.u8(L.dcls + c)));
 }
+// the walk goes on: the state is neither dead nor absorbing
+__device__ __forceinline__ bool walk_live(const Lane &L) { return L.st - 1u < L.dabs1; }
 
 // AND the end state's masks of the pass's chunks into the accumulators.
 template <bool kLds>
 __device__ __forceinline__ void slot_end(const Img<kLds> &I, Lane &L) {
-    if (L.dtrans == 0) return;  // no DFA of this pass on the slot
+    if (L.dmask == 0) return;  // no DFA of this pass on the slot
     const uint32_t nchunks = HDR_U8(I, nchunks);
     const uint32_t nc = nchunks > L.cg ? min(nchunks - L.cg, (uint32_t)kChunksPerPass) : 0;
     const uint32_t base = L.dmask + 8 * (L.st * nchunks + L.cg);
@@ -400,6 +421,37 @@ struct Cursor {
     __device__ __forceinline__ uint32_t at(uint32_t p) const { return slot[((p - w) & (kWin - 1)) ^ swz]; }
 };
 
+// One step of the pipelined walks (method, target, name, value): the
+// transition on class k out of state st -- the read the next state waits for
+// -- goes first, behind it the class of byte c1 and the byte at position p2.
+// With the image in LDS the three reads and their one wait are one asm block:
+// left to the compiler, the class read sinks to its use at the head of the
+// next iteration, two dependent LDS round trips a byte.  The reads need no
+// bounds: c1 is a byte, p2 wraps inside the lane's slot (as Cursor::at).
+template <bool kLds>
+__device__ __forceinline__ void walk_step(const Img<kLds> &I, const Cursor &C, uint32_t trans, uint32_t row, uint32_t cls,
+                                          uint32_t &st, uint32_t &k, uint32_t c1, uint32_t p2, uint32_t &c2) {
+    const uint32_t ta = row_addr(trans, st, row, k);
+    if constexpr (kLds) {
+        const uint32_t ib = (uint32_t)(uintptr_t)I.p;
+        const uint32_t ba = (uint32_t)(uintptr_t)C.slot + (((p2 - C.w) & (kWin - 1)) ^ C.swz);
+        // each read lands in its own address register: no register beyond the
+        // three addresses, and no result can overwrite an address not yet used
+        uint32_t s_ = ib + ta, k_ = ib + cls + c1, c_ = ba;
+        asm volatile("ds_read_u16 %0, %0\n\tds_read_u8 %1, %1\n\tds_read_u8 %2, %2\n\ts_waitcnt lgkmcnt(0)"
+                     : "+v"(s_), "+v"(k_), "+v"(c_)
+                     :
+                     : "memory");
+        st = s_;
+        k = k_;
+        c2 = c_;
+    } else {
+        st = I.u16(ta);
+        k = I.u8(cls + c1);
+        c2 = C.at(p2);
+    }
+}
+
 // First byte at or after pa (and before lim, inside the window) that ends a
 // token, 16 bytes a step: kKind 0 = request target (<= 0x20 or DEL), 1 =
 // header value (CTL other than HT, or DEL), 2 = simple header name (not
@@ -428,8 +480,7 @@ __device__ __forceinline__ void ows_done(const Img<kLds> &I, Lane &L) {
         if (L.slot != kNoSlot) {
             slot_begin(I, L, L.slot);
         } else {
-            L.st = 0;
-            L.dcls = L.dtrans = 0;
+            null_dfa(L);
         }
         L.in_ows = false;
         L.clv = 0;
@@ -531,23 +582,20 @@ __device__ __forceinline__ void parse_window(const Img<kLds> &I, Lane &L, Cursor
 
     // ---- request line
     if (L.mode == M_METHOD) {  // 1*tchar SP
-        // software pipeline as for the target: byte p+2 and the class of byte
-        // p+1 are read while the transition on byte p is in flight
+        // software pipeline as for the target
         uint32_t c = 0;
         if (L.pa < lim) {
             c = C.at(L.pa);
-            uint32_t k = L.dcls ? I.u8(L.dcls + c) : 0;
-            uint32_t c1 = L.pa + 1 < lim ? C.at(L.pa + 1) : 0;
-            while (is_tchar(c)) {
-                const uint32_t p1 = L.pa + 1;
-                const uint32_t c2 = p1 + 1 < lim ? C.at(p1 + 1) : 0;
-                const uint32_t k1 = L.dcls ? I.u8(L.dcls + c1) : 0;
-                if (L.st) L.st = I.u16(L.dtrans + 2 * (L.st * L.dncls + k));
-                L.pa = p1;
-                if (p1 >= lim) break;
+            uint32_t k = I.u8(L.dcls + c);
+            uint32_t c1 = C.at(L.pa + 1);
+            bool go = is_tchar(c);
+            while (go) {
+                uint32_t c2;
+                walk_step(I, C, L.dtrans, L.drow, L.dcls, L.st, k, c1, L.pa + 2, c2);
+                L.pa++;
                 c = c1;
                 c1 = c2;
-                k = k1;
+                go = (L.pa < lim) & is_tchar(c);
             }
         }
         if (L.pa < lim) {
@@ -566,21 +614,22 @@ __device__ __forceinline__ void parse_window(const Img<kLds> &I, Lane &L, Cursor
     if (L.mode == M_TARGET) {  // 1*(VCHAR / obs-text) SP
         uint32_t c = 0;
         if (L.pa < lim) {
-            // software pipeline: byte p+2 and the class of byte p+1 are read
-            // while the transition on byte p is in flight
+            // software pipeline: the transition on byte p (the read the next
+            // state waits for) is issued first, byte p+2 and the class of byte
+            // p+1 behind it.  The look-ahead reads wrap inside the lane's slot
+            // (Cursor::at) and their bytes are used only below lim; the loop
+            // has one exit, taken with c the byte at L.pa whenever L.pa < lim.
             c = C.at(L.pa);
-            uint32_t k = L.dcls ? I.u8(L.dcls + c) : 0;
-            uint32_t c1 = L.pa + 1 < lim ? C.at(L.pa + 1) : 0;
-            while (c > 0x20 && c != 0x7F && L.st != 0 && L.st < L.dabs) {
-                const uint32_t p1 = L.pa + 1;
-                const uint32_t c2 = p1 + 1 < lim ? C.at(p1 + 1) : 0;
-                const uint32_t k1 = L.dcls ? I.u8(L.dcls + c1) : 0;
-                if (L.st) L.st = I.u16(L.dtrans + 2 * (L.st * L.dncls + k));
-                L.pa = p1;
-                if (p1 >= lim) break;
+            uint32_t k = I.u8(L.dcls + c);
+            uint32_t c1 = C.at(L.pa + 1);
+            bool go = (c > 0x20) & (c != 0x7F) & walk_live(L);
+            while (go) {
+                uint32_t c2;
+                walk_step(I, C, L.dtrans, L.drow, L.dcls, L.st, k, c1, L.pa + 2, c2);
+                L.pa++;
                 c = c1;
                 c1 = c2;
-                k = k1;
+                go = (L.pa < lim) & (c > 0x20) & (c != 0x7F) & walk_live(L);
             }
         }
         if (L.pa < lim && c > 0x20 && c != 0x7F) {  // absorbing state: the rest of the target cannot change it
@@ -650,17 +699,15 @@ __device__ __forceinline__ void parse_window(const Img<kLds> &I, Lane &L, Cursor
             if (L.pa < lim) {
                 c = C.at(L.pa);
                 uint32_t k = I.u8(name_cls + c);  // 0 = not a tchar
-                uint32_t c1 = L.pa + 1 < lim ? C.at(L.pa + 1) : 0;
-                while (k != 0 && L.nstate != kNameOther) {
-                    const uint32_t p1 = L.pa + 1;
-                    const uint32_t c2 = p1 + 1 < lim ? C.at(p1 + 1) : 0;
-                    const uint32_t k1 = I.u8(name_cls + c1);
-                    L.nstate = I.u16(name_trans + 2 * (L.nstate * ncls_name + k));
-                    L.pa = p1;
-                    if (p1 >= lim) break;
+                uint32_t c1 = C.at(L.pa + 1);
+                bool go = (k != 0) & (L.nstate != kNameOther);
+                while (go) {
+                    uint32_t c2;
+                    walk_step(I, C, name_trans, 2 * ncls_name, name_cls, L.nstate, k, c1, L.pa + 2, c2);
+                    L.pa++;
                     c = c1;
                     c1 = c2;
-                    k = k1;
+                    go = (L.pa < lim) & (k != 0) & (L.nstate != kNameOther);
                 }
                 if (L.pa < lim && k != 0) {
                     // a name the rule set does not know (the DFA state loops on
@@ -698,23 +745,21 @@ __device__ __forceinline__ void parse_window(const Img<kLds> &I, Lane &L, Cursor
             uint32_t c = 0, nx = 0;  // nx: the byte after c when in hand (| 0x100)
             if (L.pa < lim) {
                 c = C.at(L.pa);
-                uint32_t k = L.dcls ? I.u8(L.dcls + c) : 0;
-                uint32_t c1 = L.pa + 1 < lim ? C.at(L.pa + 1) : 0;
+                uint32_t k = I.u8(L.dcls + c);
+                uint32_t c1 = C.at(L.pa + 1);
                 // CR ends it, other CTLs are errors; an absorbing state outside an
                 // OWS run ends the walk (trailing OWS needs the state before it)
-                while (!((c < 0x20 && c != '\t') || c == 0x7F) && (L.in_ows || (L.st != 0 && L.st < L.dabs))) {
-                    const uint32_t p1 = L.pa + 1;
-                    const uint32_t c2 = p1 + 1 < lim ? C.at(p1 + 1) : 0;
-                    const uint32_t k1 = L.dcls ? I.u8(L.dcls + c1) : 0;
-                    const bool ws = c == ' ' || c == '\t';
-                    if (ws && !L.in_ows) L.saved = L.st;
+                bool go = !value_stop(c) & (L.in_ows | walk_live(L));
+                while (go) {
+                    const bool ws = (c == ' ') | (c == '\t');
+                    L.saved = (ws & !L.in_ows) ? L.st : L.saved;
                     L.in_ows = ws;
-                    if (L.st) L.st = I.u16(L.dtrans + 2 * (L.st * L.dncls + k));
-                    L.pa = p1;
-                    if (p1 >= lim) break;
+                    uint32_t c2;
+                    walk_step(I, C, L.dtrans, L.drow, L.dcls, L.st, k, c1, L.pa + 2, c2);
+                    L.pa++;
                     c = c1;
                     c1 = c2;
-                    k = k1;
+                    go = (L.pa < lim) & !value_stop(c) & (L.in_ows | walk_live(L));
                 }
                 if (L.pa + 1 < lim) nx = c1 | 0x100;
             }
@@ -1068,6 +1113,7 @@ __device__ __forceinline__ void map_span(TileMap &T, const Lane &L, uint32_t lan
 
 // Returns true when the lane-mode map also DMA'd the tile's first head
 // windows (window_packed of every lane) into the window area.
+template <int kMapDepth>
 __device__ __forceinline__ bool build_tile_map(TileMap &T, Lane &L, uint32_t lane, uint8_t *wave_lds) {
 #pragma unroll
     for (int q = 0; q < (int)kMapWords; q++) T.m[q] = 0;
@@ -1121,7 +1167,6 @@ __device__ __forceinline__ bool build_tile_map(TileMap &T, Lane &L, uint32_t lan
             qb8[q] = (uint64_t)__shfl((unsigned long long)L.base, 8 * q + (int)grp8);
             qn8[q] = (uint32_t)__shfl((int)nch, 8 * q + (int)grp8);
         }
-        constexpr int kMapDepth = 3;  // 128-byte-per-lane steps in flight
         gm_u32x4 buf[kMapDepth][8];
 #define MAP_LOAD8(s, j)                                                                                        \
     do {                                                                                                       \
@@ -1260,7 +1305,7 @@ __device__ __forceinline__ void emit(const Lane &L, const Out &O) {
 // All rounds of one tile.
 // kInit = false: the lanes' framing state is set up by the caller (latency path).
 // pre: the tile's map, already built (latency path); null: built here.
-template <bool kLds, bool kFlush = true, bool kInit = true>
+template <bool kLds, bool kFlush = true, bool kInit = true, int kMapDepth = 3>
 __device__ __forceinline__ void run_tile(Lane &L, const uint8_t *img, uint8_t *wave_lds, uint32_t lane, const Out &O,
                                          const TileMap *pre = nullptr) {
     const Img<kLds> I{img};
@@ -1277,7 +1322,7 @@ __device__ __forceinline__ void run_tile(Lane &L, const uint8_t *img, uint8_t *w
     TileMap TM;
     bool loaded = false;  // true: the first windows are in
     if (pre) TM = *pre;
-    else loaded = build_tile_map(TM, L, lane, wave_lds);
+    else loaded = build_tile_map<kMapDepth>(TM, L, lane, wave_lds);
     PH_MARK(2);
     Cursor C;
     C.slot = wave_lds + lane * kWin;
@@ -1323,6 +1368,10 @@ __device__ __forceinline__ uint32_t cr_mask(uint4 w) {
     return nib(eq(w.x)) | nib(eq(w.y)) << 4 | nib(eq(w.z)) << 8 | nib(eq(w.w)) << 12;
 }
 
+// The latency path's own tile maps (one request: a head of more than kLatLines
+// lines, a chunked body, a further framing pass) keep two 128-byte steps in
+// flight, not three: 32 VGPRs fewer where this kernel's registers run out.
+constexpr int kLatMapDepth = 2;
 constexpr uint32_t kLatLines = 63;  // header lines one wave frames side by side (lane k: line k)
 
 // One request per wave, for the small calls of the synchronous drop-ins (one
@@ -1442,7 +1491,7 @@ __device__ __forceinline__ void lat_request(const Lane &L, const uint8_t *img, u
             W.base = 0;
             W.a0 = W.pa = W.lena = 0;
         }
-        run_tile<kLds>(W, img, wave_lds, lane, O);
+        run_tile<kLds, true, true, kLatMapDepth>(W, img, wave_lds, lane, O);
         return;
     }
     // ---- lane k: line k
@@ -1478,8 +1527,7 @@ __device__ __forceinline__ void lat_request(const Lane &L, const uint8_t *img, u
             for (int c = 0; c < kChunksPerPass; c++) W.acc[c] = ~0ull;
             W.pa = W.mark = start;
             W.mode = M_LINE;
-            W.st = 0;
-            W.dcls = W.dtrans = W.dmask = W.dncls = W.dabs = 0;
+            null_dfa(W);
             W.slot = kNoSlot;
         }
     } else {
@@ -1487,7 +1535,7 @@ __device__ __forceinline__ void lat_request(const Lane &L, const uint8_t *img, u
         W.base = 0;
         W.a0 = W.pa = W.lena = 0;
     }
-    run_tile<kLds, true, false>(W, img, wave_lds, lane, O, &TM);
+    run_tile<kLds, true, false, kLatMapDepth>(W, img, wave_lds, lane, O, &TM);
     LAT_T(10);
     // ---- merge (a line that reached its end finished INCOMPLETE there)
     const bool bad = act && W.verdict == V_PARSE_ERROR;
@@ -1537,7 +1585,7 @@ __device__ __forceinline__ void lat_request(const Lane &L, const uint8_t *img, u
             headers_done(I, W, O.nfa_bits);
         }
     }
-    if (__ballot(lane == 0 && !W.done)) run_tile<kLds, true, false>(W, img, wave_lds, lane, O);  // body / next pass
+    if (__ballot(lane == 0 && !W.done)) run_tile<kLds, true, false, kLatMapDepth>(W, img, wave_lds, lane, O);  // body / next pass
     else if (lane == 0) emit(W, O);
     LAT_T(11);
 }
