@@ -43,6 +43,8 @@ EXPORTS = (
     "l7g_flow_stats_enable", "l7g_flow_stats",
     "l7g_tables_export", "l7g_tables_import", "l7g_tables_compiled", "l7g_tables_digest",
     "l7g_frame_streams", "l7g_classify_streams", "l7g_service_enable", "l7g_service_stats",
+    "l7g_cass_sessions_enable", "l7g_cass_replies", "l7g_cass_replies_host", "l7g_cass_session_reset",
+    "l7g_cass_session_stats",
 )
 
 
@@ -92,6 +94,12 @@ def load(path=None):
     lib.l7g_classify_streams.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                          vp, vp, vp]
     lib.l7g_classify_host.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp]
+    lib.l7g_cass_sessions_enable.argtypes = [vp, C.c_uint32, cp, sz]
+    lib.l7g_cass_replies.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp]
+    lib.l7g_cass_replies_host.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp]
+    lib.l7g_cass_session_reset.argtypes = [vp, vp, C.c_uint32]
+    lib.l7g_cass_session_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.l7g_cass_session_stats.restype = None
     lib.l7g_service_enable.argtypes = [vp, C.c_int]
     lib.l7g_service_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.l7g_service_stats.restype = None

@@ -67,6 +67,7 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
     if (e->device < 0) return (int)hipErrorNoDevice;
     hipError_t rc = hipSetDevice(e->device);
     if (rc == hipSuccess) rc = Upload(e);
+    if (rc == hipSuccess) rc = SessionsSync(e);
     if (rc != hipSuccess) return (int)rc;
     hipStream_t s = (hipStream_t)stream;
     const Batch B{arena, arena_len, off, len, conn, e->d_conns, verdict, rule, consumed, n, (uint32_t)e->conns.size()};
@@ -256,11 +257,16 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
     // r2d2 (proxylib's example line protocol): one lane per request over the whole batch
     if (rc == hipSuccess && run_r2) rc = LaunchR2d2Classify(B, rt, !partitioned, big_lanes, s);
     // cassandra (proxylib): the batch's USE requests, then one lane per request
+    // (with sessions on: against the session tables, then the batch's USE and PREPARE requests committed)
     if (rc == hipSuccess && run_cs) {
-        const size_t need = CassandraScratchBytes(n);
+        const bool sessions = e->sess.by_id != nullptr;
+        const size_t need = CassandraScratchBytes(n, sessions);
         if (need == 0) rc = hipErrorInvalidValue;
         if (rc == hipSuccess) rc = S->Grow(&S->d_use, &S->use_cap, need, need);
-        if (rc == hipSuccess) rc = LaunchCassandraClassify(B, ct, S->d_use, S->use_cap, !partitioned, big_lanes, s);
+        if (rc == hipSuccess && sessions)
+            rc = LaunchCassandraSessionClassify(B, ct, e->sess, S->d_use, S->use_cap, !partitioned, big_lanes, s);
+        else if (rc == hipSuccess)
+            rc = LaunchCassandraClassify(B, ct, S->d_use, S->use_cap, !partitioned, big_lanes, s);
     }
     mark(4);
     // proxy statistics (accumulated on the device until read)
@@ -297,7 +303,36 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
     return (int)rc;
 }
 
+// l7g_cass_replies: the replies framed, the RESULT/prepared ones bound, on the
+// caller's stream with that stream's cassandra scratch.
+int CassReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream) {
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->device < 0) return (int)hipErrorNoDevice;
+    if (!e->sess.by_id) return (int)hipErrorNotReady;  // sessions are off: nothing to bind into
+    hipError_t rc = hipSetDevice(e->device);
+    if (rc == hipSuccess) rc = Upload(e);
+    if (rc == hipSuccess) rc = SessionsSync(e);
+    if (rc != hipSuccess || n == 0) return (int)rc;
+    hipStream_t s = (hipStream_t)stream;
+    StreamScratch *S = nullptr;
+    if ((rc = GetScratch(e, s, &S)) != hipSuccess) return (int)rc;
+    const size_t need = CassandraScratchBytes(n);
+    if (need == 0) return (int)hipErrorInvalidValue;
+    rc = S->Grow(&S->d_use, &S->use_cap, need, need);
+    const Batch B{arena, arena_len, off, len, conn, e->d_conns, verdict, nullptr, consumed, n, (uint32_t)e->conns.size()};
+    if (rc == hipSuccess) rc = LaunchCassandraReplies(B, e->sess, S->d_use, S->use_cap, s);
+    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
+    if (rc == hipSuccess) S->launched = true;
+    return (int)rc;
+}
+
 extern "C" {
+
+int l7g_cass_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                     const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream) {
+    return CassReplies(e, arena, arena_len, off, len, conn, n, verdict, consumed, stream);
+}
 
 int l7g_classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
                  const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed,

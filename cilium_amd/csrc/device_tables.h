@@ -411,6 +411,46 @@ struct CassTables {
     uint64_t *nfa_scratch;     // large NFAs: nfa_lane_words per lane of the launch (null: none in the pool)
     uint32_t nfa_lane_words;
 };
+// Cassandra sessions (l7g_cass_sessions_enable; kernels/cassandra_session.hip):
+// what proxylib's parser keeps per connection, resident in HBM.
+constexpr uint32_t kCassKsMax = 256;    // keyspace token bytes a slot holds
+constexpr uint32_t kCassPathMax = 240;  // parts[3] bytes a statement holds
+constexpr uint32_t kCassIdMax = 64;     // prepared-id bytes a statement is bound under
+constexpr uint32_t kCassOver = 0xFFFFFFFFu;  // ks_len / path_len: over its cap (requests needing it: UNSUPPORTED)
+constexpr int32_t kCassTomb = -2;       // CassEntry::action: the binding is void (EXECUTE answers unprepared)
+// One per connection index: the keyspace as the raw trimmed token of its USE
+// query (cass_seg3 lowers it as it emits) and that query's fc rebased to the token.
+struct CassSlot {  // 272 B
+    uint32_t gen;      // entries claimed under another generation no longer resolve
+    uint32_t ks_len;   // bytes of ks; kCassOver = the token did not fit
+    uint32_t ks_fc;    // first rune strings.ToLower changes, token-relative (~0u = none)
+    uint32_t dropped;  // a PREPARE of this connection found the stream table full
+    uint8_t ks[kCassKsMax];
+};
+static_assert(sizeof(CassSlot) == 272, "CassSlot layout");
+// One statement of an open-addressed table (linear probing).  claim: 0 = never
+// used (ends a probe chain), else (connection + 1) << 32 | generation; the key
+// (stream id, 2 bytes big endian, or the prepared id) is compared in full.
+struct CassEntry {  // 328 B
+    unsigned long long claim;
+    int32_t action;     // CA_*, -1 = outside queryActionMap, kCassTomb
+    uint32_t key_len;
+    uint32_t path_len;  // bytes of path (0: parts[3] is empty); kCassOver
+    uint32_t pad;
+    uint8_t key[kCassIdMax];
+    uint8_t path[kCassPathMax];
+};
+static_assert(sizeof(CassEntry) == 328, "CassEntry layout");
+enum : int { CSS_DROPPED = 0, CSS_OVERFLOW = 1, CSS_RESOLVED = 2, CSS_UNPREPARED = 3, CSS_WORDS = 4 };
+struct CassSessions {
+    CassSlot *slots;       // null: sessions are off
+    uint32_t nslots;
+    uint32_t mask;         // table capacity - 1 (a power of two)
+    CassEntry *by_stream;  // written by PREPARE requests
+    CassEntry *by_id;      // written by RESULT/prepared replies, read by EXECUTE
+    unsigned long long *stats;  // CSS_*
+};
+
 #if defined(__HIPCC__)
 // A lane's large-NFA scratch (2 W words), by its index in the launch
 __device__ __forceinline__ uint64_t *l7_nfa_lane_scratch(uint64_t *base, uint32_t words) {

@@ -228,6 +228,13 @@ struct l7g_engine {
     bool flow_stats = false;
     uint64_t *d_flow = nullptr;
     size_t flow_cap = 0;  // keys the accumulator holds
+    // cassandra sessions (l7g_cass_sessions_enable; on while sess.by_id is set):
+    // the device tables (kernels/cassandra_session.hip), one slot per connection
+    // index grown with the connection table, and the new-connection events
+    // since the last launch (applied by SessionsSync before the next one)
+    CassSessions sess{};
+    std::vector<uint32_t> sess_reset;
+    bool sess_reset_all = false;
     // Every stream's last completion event (StreamScratch::done_ev) is waited
     // on -- never a caller's stream, which may be gone by then -- before the
     // engine rewrites or frees anything a launched kernel reads: the
@@ -283,6 +290,12 @@ inline bool SpinUntil(Load load, uint32_t seq, std::chrono::milliseconds limit) 
 
 hipError_t Upload(l7g_engine *e);            // capi.cc (e->mu held)
 hipError_t WaitLastClassify(l7g_engine *e);  // classify.cc (e->mu held), as Classify (takes e->mu)
+// capi.cc (e->mu held): with sessions on, a slot for every connection and the pending resets applied
+hipError_t SessionsSync(l7g_engine *e);
+void SessionsFree(l7g_engine *e);
+// classify.cc: l7g_cass_replies (device pointers; takes e->mu)
+int CassReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream);
 int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
              const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed, uint64_t *counters,
              void *stream, const uint32_t *host_conn, const CopyIn *pre = nullptr, bool *signaled = nullptr);

@@ -274,4 +274,38 @@ int l7g_classify_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, c
     return HostRunStaged(e, n, arena_len, verdict, rule, consumed, false);
 }
 
+// l7g_cass_replies with host buffers, over the calling thread's stream and
+// staging: one copy in, the reply kernels, one copy out, a wait.
+int l7g_cass_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                          const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed) {
+    uint8_t *pa;
+    uint64_t *po;
+    uint32_t *pl, *pc;
+    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
+    if (rc0 != 0) return rc0;
+    if (n) {
+        memcpy(po, off, (size_t)n * 8);
+        memcpy(pl, len, (size_t)n * 4);
+        memcpy(pc, conn, (size_t)n * 4);
+    }
+    if (arena_len) memcpy(pa, arena, arena_len);
+    HostCtx *H = nullptr;
+    hipError_t rc = HostEnter(e, &H);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t nn = CallNn(n);
+    uint8_t *d_in = H->dev, *d_out = H->dev + H->in_cap;
+    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
+    if (rc == hipSuccess)
+        rc = (hipError_t)CassReplies(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
+                                     (const uint32_t *)(d_in + CallLenOff(nn)), (const uint32_t *)(d_in + CallConnOff(nn)),
+                                     n, d_out, (uint32_t *)(d_out + CallConsumedOff(n)), H->s);
+    if (rc == hipSuccess && n) rc = hipMemcpyAsync(H->pin_out, d_out, CallOutBytes(n), hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
+    if (rc == hipSuccess && n) {
+        memcpy(verdict, H->pin_out, n);
+        memcpy(consumed, H->pin_out + CallConsumedOff(n), (size_t)n * 4);
+    }
+    return (int)rc;
+}
+
 }  // extern "C"

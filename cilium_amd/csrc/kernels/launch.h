@@ -25,9 +25,19 @@ hipError_t LaunchMemcacheClassify(const Batch &B, const McTables &T, const uint3
                                   hipStream_t stream, const CopyIn *ci = nullptr);
 hipError_t LaunchR2d2Classify(const Batch &B, const R2Tables &T, bool answer_other, uint32_t scratch_lanes,
                               hipStream_t stream);
-size_t CassandraScratchBytes(uint32_t n);
+size_t CassandraScratchBytes(uint32_t n, bool sessions = false);
 hipError_t LaunchCassandraClassify(const Batch &B, const CassTables &T, void *scratch, size_t scratch_bytes,
                                    bool answer_other, uint32_t nfa_lanes, hipStream_t stream);
+// cassandra sessions (kernels/cassandra_session.hip): classify against the session tables and commit the batch
+hipError_t LaunchCassandraSessionClassify(const Batch &B, const CassTables &T, const CassSessions &SS, void *scratch,
+                                          size_t scratch_bytes, bool answer_other, uint32_t nfa_lanes,
+                                          hipStream_t stream);
+hipError_t LaunchCassandraCommit(const Batch &B, const CassTables &T, const CassSessions &S,
+                                 const uint64_t *use_sorted, const uint64_t *prep_sorted, hipStream_t stream);
+hipError_t LaunchCassandraReplies(const Batch &B, const CassSessions &S, void *scratch, size_t scratch_bytes,
+                                  hipStream_t stream);
+hipError_t LaunchCassandraSessionReset(const CassSessions &S, const uint32_t *conn, uint32_t n, hipStream_t stream);
+hipError_t LaunchCassandraSessionLive(const CassSessions &S, unsigned long long *out2, hipStream_t stream);
 hipError_t LaunchCounters(const uint8_t *verdict, const int32_t *rule, uint32_t n, uint32_t nrules,
                           uint64_t *counters, uint32_t *scratch, hipStream_t stream);
 size_t CountersScratchBytes();

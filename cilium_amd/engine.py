@@ -144,6 +144,60 @@ class Engine:
             raise RuntimeError(f"l7g_classify_host failed: HIP error {rc}")
         return v, r, c
 
+    # ---------------------------------------------------- cassandra sessions
+    def cass_sessions(self, max_statements):
+        """Device-resident cassandra sessions (l7g_cass_sessions_enable): with
+        max_statements > 0 the engine keeps each connection's keyspace and
+        prepared statements across classify calls; 0 turns them off."""
+        err = C.create_string_buffer(512)
+        rc = self._lib.l7g_cass_sessions_enable(self._h, int(max_statements), err, 512)
+        if rc != 0:
+            raise RuntimeError(f"l7g_cass_sessions_enable: HIP error {rc}: " + err.value.decode(errors="replace"))
+
+    def cass_replies(self, arena, offsets, lengths, conn_ids):
+        """The reply direction of cassandra connections (host buffers): frames
+        each reply and binds RESULT/prepared ids; returns (verdict, consumed)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        n = len(off)
+        v = np.zeros(n, np.uint8)
+        c = np.zeros(n, np.uint32)
+        rc = self._lib.l7g_cass_replies_host(self._h, arena.ctypes.data, arena.nbytes, off.ctypes.data,
+                                             ln.ctypes.data, cid.ctypes.data, n, v.ctypes.data, c.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"l7g_cass_replies_host failed: HIP error {rc}")
+        return v, c
+
+    def cass_replies_device(self, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, verdict_ptr, consumed_ptr,
+                            stream=0):
+        """l7g_cass_replies: all pointers are device addresses."""
+        rc = self._lib.l7g_cass_replies(self._h, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, verdict_ptr,
+                                        consumed_ptr, stream or None)
+        if rc != 0:
+            raise RuntimeError(f"l7g_cass_replies failed: HIP error {rc}")
+
+    def cass_session_reset(self, conn_ids):
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        rc = self._lib.l7g_cass_session_reset(self._h, cid.ctypes.data, len(cid))
+        if rc != 0:
+            raise RuntimeError(f"l7g_cass_session_reset failed: HIP error {rc}")
+
+    SESSION_STATS = ("stream_entries", "id_entries", "dropped", "overflows", "resolved", "unprepared")
+
+    def cass_session_stats(self):
+        out = (C.c_uint64 * 6)()
+        self._lib.l7g_cass_session_stats(self._h, out)
+        return dict(zip(self.SESSION_STATS, [int(x) for x in out]))
+
+    def conn_update(self, index, conn):
+        """One connection set (or added) alone: l7g_conn_update, the new-connection event."""
+        arr = conns_array([conn])
+        err = C.create_string_buffer(1024)
+        if self._lib.l7g_conn_update(self._h, int(index), arr.ctypes.data, err, 1024) != 0:
+            raise PolicyError(err.value.decode(errors="replace"))
+
     STAGES = ("partition", "http", "kafka", "memcache")
 
     def profile(self, on=True):

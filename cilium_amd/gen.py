@@ -1160,3 +1160,125 @@ def cassandra_workload(n, nconns=16, seed=None):
     remotes = [7, 8, 100, 101, 150, 163, 5] * (nconns // 7 + 1)
     conns = make_conns(nconns, 0, CASS_PORT, True, PROTO_CASSANDRA, remotes[:nconns])
     return Workload("cassandra", arena, offs, lens, conn_ids, conns, cassandra_policy())
+
+
+# ------------------------------------------------------- cassandra sessions
+# A connection's life across batches (l7g_cass_sessions_enable): USE once,
+# PREPARE, the RESULT/prepared reply that binds the statement to an id, then
+# mostly EXECUTE.  Caps of the device tables (include/l7gpu.h): every id,
+# table part and keyspace a script holds stays inside them, so the oracle's
+# answer is the expected one for every frame.
+CASS_ID_MAX, CASS_TABLE_MAX, CASS_KS_MAX = 64, 240, 256
+
+_CASS_KEYSPACES = ["ks1", "KS1", "ks2", "\"Ks2\"", "'system'", "wild", "ks/x", "été", "k\udcffs", "''"]
+_CASS_STATEMENTS = [
+    "select * from users", "SELECT a FROM ks1.users WHERE id = ?", "select * from local", "select * from system.local",
+    "insert into users (a) values (?)", "INSERT INTO ks2.users (a) VALUES (?)", "update t set a = ?",
+    "UPDATE été SET a = ?", "update ÉTÉ set b = ?", "delete from old where x = ?", "delete from ks1.old",
+    "drop table if exists .tmp1", "drop table tmpx", "create index i on t (a)", "create a/bab c", "list roles",
+    "truncate table t", "select * from wildcat", "select * from cat", "use ks1", "USE \"KS2\"",
+    "select * from " + "ab" * 3 + "a" + "ab" * 7, "select * from bbbbbbbbbbbbbbbbbbbb", "select * from t\udcff",
+    "select * from T\udcffx", "select * from", "select", "select * from t -- c", "insert into", "grant select on t to r",
+]
+
+
+def cass_execute_frame(prepared_id, stream=1, trailer=b"\x00\x01\x00"):
+    return cass_frame(0x0A, len(prepared_id).to_bytes(2, "big") + prepared_id + trailer, stream)
+
+
+def cass_prepared_reply(prepared_id, stream=1, kind=4, trailer=b"\x00\x00\x00\x00"):
+    """RESULT (0x08) of the given kind in the reply direction; kind 4 = prepared: [short bytes] id."""
+    body = kind.to_bytes(4, "big") + len(prepared_id).to_bytes(2, "big") + prepared_id + trailer
+    return cass_frame(0x08, body, stream, version=0x84)
+
+
+def cassandra_session_script(nconns=64, rounds=30, nreq=256, nrep=96, seed=None):
+    """A session script: (conns, policy, rounds); each round is a dict with one
+    request batch (requests, req_conn) and the reply batch that follows it
+    (replies, rep_conn).  Requests: USE, QUERY, PREPARE (on a few stream ids per
+    connection, so statements are replaced), EXECUTE of ids that are bound,
+    prepared but not yet bound, bound on another connection and never prepared,
+    BATCH, other opcodes, truncated and reply-direction frames.  Replies:
+    RESULT/prepared on stream ids that match a PREPARE or miss, other RESULT
+    kinds, other opcodes, truncated frames, request-direction frames."""
+    seed = SEED_BASE + 31 if seed is None else seed
+    rng = np.random.default_rng(seed)
+    remotes = [7, 8, 100, 101, 150, 163, 5] * (nconns // 7 + 1)
+    conns = make_conns(nconns, 0, CASS_PORT, True, PROTO_CASSANDRA, remotes[:nconns])
+    # a few ids per connection (rebinding happens), lengths 0 .. CASS_ID_MAX, some shared between connections
+    shared = [b"", b"ab", bytes(range(16)), b"\xff" * CASS_ID_MAX]
+    ids = [shared + [bytes(rng.integers(0, 256, size=int(rng.integers(1, CASS_ID_MAX + 1)), dtype=np.uint8))
+                     for _ in range(6)] for _ in range(nconns)]
+    never = [b"never", b"\x00" * 16, b"n" * CASS_ID_MAX]
+    pending = [dict() for _ in range(nconns)]   # stream -> a PREPARE went out on it
+    bound = [set() for _ in range(nconns)]      # indices into ids[c] some reply bound
+    answered = [list() for _ in range(nconns)]  # indices a reply will carry next (prepared, not yet bound)
+
+    def statement():
+        b = _CASS_STATEMENTS[int(rng.integers(0, len(_CASS_STATEMENTS)))].encode("utf-8", "surrogateescape")
+        if rng.random() < 0.04:
+            b = b.replace(b"t", b"\xfe", 1)
+        return b
+
+    out = []
+    for _ in range(rounds):
+        reqs, rc = [], rng.integers(0, nconns, size=nreq).astype(np.uint32)
+        for c in rc.tolist():
+            k = float(rng.random())
+            stream = int(rng.integers(0, 6))
+            if k < 0.08:
+                ks = _CASS_KEYSPACES[int(rng.integers(0, len(_CASS_KEYSPACES)))].encode("utf-8", "surrogateescape")
+                reqs.append(cass_query_frame(b"use " + ks, 0x09 if rng.random() < 0.15 else 0x07, stream))
+            elif k < 0.30:
+                reqs.append(cass_query_frame(statement(), 0x07, stream))
+            elif k < 0.44:
+                reqs.append(cass_query_frame(statement(), 0x09, stream))
+                pending[c][stream] = True
+                answered[c].append(int(rng.integers(0, len(ids[c]))))
+            elif k < 0.80:
+                u = float(rng.random())
+                if u < 0.55 and bound[c]:
+                    pid = ids[c][int(rng.choice(sorted(bound[c])))]
+                elif u < 0.70 and answered[c]:
+                    pid = ids[c][answered[c][int(rng.integers(0, len(answered[c])))]]   # prepared, maybe not yet bound
+                elif u < 0.85:
+                    pid = ids[int(rng.integers(0, nconns))][int(rng.integers(0, len(ids[c])))]  # another connection's
+                else:
+                    pid = never[int(rng.integers(0, len(never)))]
+                reqs.append(cass_execute_frame(pid, stream))
+            elif k < 0.83:
+                reqs.append(cass_frame(0x0D, b"\x00\x00\x01\x00\x00\x00\x00\x04use x", stream))  # BATCH: panics
+            elif k < 0.90:
+                reqs.append(cass_frame(int(rng.choice([0x01, 0x05, 0x0B, 0x0F, 0x20])), b"\x00" * int(rng.integers(0, 8)), stream))
+            elif k < 0.95:
+                f = cass_query_frame("select * from ks1.t", 0x09 if rng.random() < 0.5 else 0x07, stream)
+                reqs.append(f[:int(rng.integers(0, len(f)))])                                    # truncated
+            elif k < 0.97:
+                body = b"\x00" if rng.random() < 0.3 else (40).to_bytes(2, "big") + b"abc"
+                reqs.append(cass_frame(0x0A, body, stream))                                      # EXECUTE: id past the buffer
+            else:
+                f = bytearray(cass_query_frame("use ks2", 0x07, stream))
+                f[int(rng.choice([0, 1]))] |= int(rng.choice([0x80, 0x01]))                      # reply bit / compressed
+                reqs.append(bytes(f))
+        reps, pc = [], rng.integers(0, nconns, size=nrep).astype(np.uint32)
+        for c in pc.tolist():
+            k = float(rng.random())
+            j = answered[c].pop(0) if answered[c] else int(rng.integers(0, len(ids[c])))
+            if k < 0.70 and pending[c]:
+                stream = int(rng.choice(sorted(pending[c])))
+                reps.append(cass_prepared_reply(ids[c][j], stream))
+                bound[c].add(j)
+            elif k < 0.80:
+                reps.append(cass_prepared_reply(ids[c][j], int(rng.integers(6, 65536))))          # no such stream
+            elif k < 0.87:
+                reps.append(cass_prepared_reply(ids[c][j], int(rng.integers(0, 6)), kind=int(rng.choice([1, 2, 3, 5]))))
+            elif k < 0.92:
+                reps.append(cass_frame(int(rng.choice([0x00, 0x02, 0x06, 0x10])), b"\x00" * int(rng.integers(0, 6)),
+                                       int(rng.integers(0, 6)), version=0x84))
+            elif k < 0.97:
+                f = cass_prepared_reply(ids[c][j], int(rng.integers(0, 6)))
+                reps.append(f[:int(rng.integers(0, len(f)))])                                    # truncated
+            else:
+                reps.append(cass_frame(0x08, (4).to_bytes(4, "big") + b"\x00\x02ab", int(rng.integers(0, 6))))  # request direction
+        out.append({"requests": reqs, "req_conn": rc, "replies": reps, "rep_conn": pc})
+    return conns, cassandra_policy(), out

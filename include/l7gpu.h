@@ -45,14 +45,19 @@ extern "C" {
 typedef struct l7g_engine l7g_engine;
 
 enum { L7G_PROTO_HTTP = 1, L7G_PROTO_KAFKA = 2, L7G_PROTO_MEMCACHE = 3, L7G_PROTO_R2D2 = 4, L7G_PROTO_CASSANDRA = 5 };
-/* L7G_PROTO_CASSANDRA keeps no state between l7g_classify calls: a request's
- * keyspace comes only from the last USE on its connection earlier in the same
- * batch (a USE from an earlier batch is not remembered, so "t" stays ".t"
- * rather than "ks.t"), and an EXECUTE is never resolved to its prepared query
- * (answered L7G_PARSE_ERROR, consumed 2).  The proxylib shim keeps both per
- * connection (USE keyspace, PREPARE ids) and replays them into each batch, as
- * cassandraparser.go does; a direct caller that needs the reference's
- * cross-batch behaviour must do the same. */
+/* L7G_PROTO_CASSANDRA has two modes.
+ * Stateless (the default): nothing is kept between l7g_classify calls.  A
+ * request's keyspace comes only from the last USE on its connection earlier in
+ * the same batch (a USE from an earlier batch is not remembered, so "t" stays
+ * ".t" rather than "ks.t"), and an EXECUTE is never resolved to its prepared
+ * query (answered L7G_PARSE_ERROR, consumed 2).  The proxylib shim keeps both
+ * per connection on the host and replays them into each batch.
+ * Sessions (l7g_cass_sessions_enable, below): the engine keeps what
+ * cassandraparser.go keeps per connection -- the keyspace of the last USE, the
+ * statements PREPAREd by stream id, and their binding to prepared ids by the
+ * RESULT/prepared replies given to l7g_cass_replies -- in device memory, and
+ * l7g_classify / l7g_classify_host give the reference's answers across
+ * batches, EXECUTE included, with no host pass over the bytes. */
 enum {
     L7G_DENY = 0,        /* policy denies (HTTP 403 / Kafka ErrTopicAuthorizationFailed) */
     L7G_ALLOW = 1,       /* policy allows; rule = matched global rule id or -1 */
@@ -209,6 +214,69 @@ int l7g_classify_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, c
                       uint32_t *consumed);
 
 int l7g_stats(l7g_engine *e, l7g_stats_t *out);
+
+/* Cassandra sessions (off by default; with them off every answer is the
+ * stateless one, byte for byte).
+ *
+ * l7g_cass_sessions_enable: max_statements > 0 turns them on (again: all
+ * sessions start empty), 0 turns them off and frees the tables.  Two
+ * open-addressed tables are allocated, statements by (connection, stream id)
+ * and by (connection, prepared id), each with room for at least
+ * max_statements entries (twice that, rounded up to a power of two; at most
+ * 2^24 statements), and one 272-byte slot per connection index, grown with the
+ * connection table.  A host-only engine returns hipErrorNoDevice.
+ *
+ * With sessions on, a request batch is classified against the state as it
+ * stood before the call -- except the keyspace, which inside a batch is that
+ * of the last USE before the request on its connection, and before the
+ * batch's first USE the stored one -- and then committed in batch order per
+ * connection: the last USE becomes the stored keyspace; every PREPARE whose
+ * query parses is stashed under its stream id, whatever its verdict, with the
+ * keyspace in force at its position (last PREPARE wins).  An EXECUTE whose id
+ * was bound before its call began is matched against the connection's current
+ * rule set (ALLOW with the rule id or DENY, consumed = the frame length); any
+ * other id answers L7G_PARSE_ERROR, consumed 2, as in the stateless mode.
+ *
+ * l7g_cass_replies takes the reply direction: n buffers on device memory, as
+ * l7g_classify takes requests.  Each is framed as cassandraparser.go frames a
+ * reply (INCOMPLETE with the missing byte count; PARSE_ERROR 3 for a body over
+ * 256 MB; PARSE_ERROR 0 where the parser panics; otherwise ALLOW, consumed =
+ * the frame length -- replies are never denied), and a RESULT/prepared reply
+ * binds the statement stashed under its stream id, as it stood before the
+ * call, to its prepared id (last reply wins).  A buffer on a connection that
+ * is not Cassandra answers L7G_UNSUPPORTED.  Returns hipErrorNotReady while
+ * sessions are off.  l7g_cass_replies_host is the same on host buffers
+ * (copies in, runs, copies out, synchronises; the calling thread's stream).
+ *
+ * Limits: a keyspace over 256 bytes, a table part over 240 bytes or a
+ * prepared id over 64 bytes does not fit.  Requests that would need such a
+ * keyspace or table answer L7G_UNSUPPORTED; such an id is not bound, so its
+ * EXECUTE answers unprepared.  A full table drops the insert: a later EXECUTE
+ * answers unprepared, which a client recovers from by preparing again.  No
+ * limit ever turns into an ALLOW or DENY the reference would not give.
+ *
+ * Resets: l7g_conn_update(index) is the new-connection event and empties that
+ * connection's session; l7g_conns_set empties all; l7g_cass_session_reset
+ * empties the named ones.  A policy update resets nothing: the stored
+ * statements are matched against the policy in force at EXECUTE.
+ *
+ * The state is engine-wide, not per stream: calls that touch one connection
+ * (its requests, its replies, its resets) must be ordered by the caller, by
+ * issuing them on one stream.  Sessions of different connections are
+ * independent, so batches over disjoint connections may run on different
+ * streams.
+ *
+ * l7g_cass_session_stats: [0] statements held by stream id, [1] by prepared
+ * id, [2] inserts dropped (table full), [3] keyspaces / tables / ids over
+ * their cap, [4] EXECUTEs resolved, [5] EXECUTEs answered unprepared; [2..5]
+ * since sessions were enabled.  Waits for the launched calls. */
+int l7g_cass_sessions_enable(l7g_engine *e, uint32_t max_statements, char *err, size_t errlen);
+int l7g_cass_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                     const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream);
+int l7g_cass_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                          const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed);
+int l7g_cass_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n);
+void l7g_cass_session_stats(l7g_engine *e, uint64_t out[6]);
 
 /* Resident services: the synchronous drop-in calls of l7g_classify_host (and
  * so the Envoy adapter's Allowed() and proxylib's OnData) whose requests are
