@@ -34,7 +34,8 @@ constexpr int kCntMc = L7_KAFKA_CLASSES;           // memcached retrievals (bina
 constexpr int kCntHttp = L7_KAFKA_CLASSES + 2;     // HTTP
 constexpr int kCntMcText2 = L7_KAFKA_CLASSES + 3;  // memcached text commands other than retrievals
 constexpr int kCntKafkaWork = 26;                  // the Kafka kernel's entry counter
-constexpr int kCntHttpTiles = 28;                  // and the next word: HTTP tile counters (hot, general launch)
+constexpr int kCntMcWork = 27;                     // the memcached kernel's chunk counter (persistent grid)
+constexpr int kCntHttpTiles = 28;                 // and the next word: HTTP tile counters (hot, general launch)
 constexpr int kCntKafkaZ = 31;                     // Kafka requests with compressed messages
 // the index lists behind the block, in words: L7_KAFKA_CLASSES x n Kafka, n memcached, n HTTP, n compressed Kafka
 constexpr size_t PartitionListWords(size_t n) { return (L7_KAFKA_CLASSES + 3) * n; }

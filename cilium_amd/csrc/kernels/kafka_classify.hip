@@ -597,7 +597,8 @@ struct ExactHooks {
 template <int kWaves>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 8))) void kafka_classify_kernel(
     Batch B, KafkaTables T, const uint32_t *__restrict__ sel, const uint32_t *__restrict__ sel_count,
-    uint32_t answer_other, uint32_t *__restrict__ zlist, uint32_t *__restrict__ zcount, uint32_t *__restrict__ work) {
+    uint32_t answer_other, uint32_t *__restrict__ zlist, uint32_t *__restrict__ zcount, uint32_t *__restrict__ work,
+    uint32_t main_sweep) {
     const uint32_t n = B.n, nconns = B.nconns;
     static_assert(kBlock >= 256, "one CRC table entry per thread");
     __shared__ uint32_t crctab[kCrcTables * 256];
@@ -620,7 +621,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
     // later one either, so the loop may run divergent.
     // (Taking 2 or 4 groups per atomic: cfg3 0.62 -> 0.77 / 1.07 ms, the
     // longest-first order makes the tail longer; profiles/r5/ab5e_*.)
-    const uint32_t stride = gridDim.x * kBlock;
+    // main_sweep != 0: this launch is the helper grid beside the main one (whose
+    // first sweep is that many entries): it takes no sweep of its own, only
+    // groups from the counter, so both grids draw from one sequence and every
+    // entry is taken exactly once.
+    const uint32_t stride = main_sweep ? main_sweep : gridDim.x * kBlock;
     auto next_entry = [&](uint32_t i) -> uint32_t {
         if (!work) return i + stride;
         const uint32_t lane = threadIdx.x & 63;
@@ -628,7 +633,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
         if (lane == (uint32_t)__builtin_amdgcn_readfirstlane(lane)) t = atomicAdd(work, 64u);
         return stride + __builtin_amdgcn_readfirstlane(t) + lane;
     };
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < m; i = next_entry(i)) {
+    for (uint32_t i = main_sweep ? next_entry(0) : blockIdx.x * kBlock + threadIdx.x; i < m; i = next_entry(i)) {
         uint32_t idx = i;
         if (sel) {
             // the length classes longest first: long produce requests start first, short ones fill the tail
@@ -698,12 +703,15 @@ hipError_t KafkaPhaseTimes(uint64_t *, bool) { return hipErrorNotSupported; }
 
 // leave_per_cu > 0 (persistent grid only): that many workgroup slots per CU left
 // free for a kernel running beside this one on another stream
+// helper (with leave_per_cu > 0 and a counter): not the main grid but a second, small one for the slots
+// the main grid left, launched behind the kernel that ran in them; it draws from the same counter
 hipError_t LaunchKafkaClassify(const Batch &B, const KafkaTables &T, const uint32_t *sel, const uint32_t *sel_count,
                                bool answer_other, uint32_t *zlist, uint32_t *zcount, uint32_t *work,
-                               hipStream_t stream, int leave_per_cu) {
+                               hipStream_t stream, int leave_per_cu, bool helper) {
     if (B.n == 0) return hipSuccess;
     uint32_t blocks = (B.n + kBlock - 1) / kBlock;
     const bool beside = leave_per_cu > 0;
+    if (helper && (!beside || !work)) return hipErrorInvalidValue;
     // persistent grid: as many workgroups as the CUs hold at once (per build)
     static int cus[2] = {0, 0}, per_cu[2] = {0, 0};
     if (cus[beside] == 0) {
@@ -724,12 +732,17 @@ hipError_t LaunchKafkaClassify(const Batch &B, const KafkaTables &T, const uint3
     const int slots = beside && pc > leave_per_cu ? pc - leave_per_cu : pc;
     if (!work) blocks = blocks > 8192 ? 8192 : blocks;  // grid-stride beyond this
     else if (blocks > (uint32_t)(cus[beside] * slots)) blocks = (uint32_t)(cus[beside] * slots);
-    if (beside)
+    if (helper) {
+        // (blocks: the main grid's, as its launch computed them)
+        const uint32_t mine = min(blocks, (uint32_t)(cus[beside] * min(leave_per_cu, pc)));
+        hipLaunchKernelGGL(kafka_classify_kernel<6>, dim3(mine), dim3(kBlock), 0, stream, B, T, sel, sel_count,
+                           answer_other ? 1u : 0u, zlist, zcount, work, blocks * (uint32_t)kBlock);
+    } else if (beside)
         hipLaunchKernelGGL(kafka_classify_kernel<6>, dim3(blocks), dim3(kBlock), 0, stream, B, T, sel, sel_count,
-                           answer_other ? 1u : 0u, zlist, zcount, work);
+                           answer_other ? 1u : 0u, zlist, zcount, work, 0u);
     else
         hipLaunchKernelGGL(kafka_classify_kernel<5>, dim3(blocks), dim3(kBlock), 0, stream, B, T, sel, sel_count,
-                           answer_other ? 1u : 0u, zlist, zcount, work);
+                           answer_other ? 1u : 0u, zlist, zcount, work, 0u);
     return hipGetLastError();
 }
 

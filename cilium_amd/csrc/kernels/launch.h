@@ -15,14 +15,15 @@ hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const uint32_
                               hipStream_t stream);
 hipError_t LaunchKafkaClassify(const Batch &B, const KafkaTables &T, const uint32_t *sel, const uint32_t *sel_count,
                                bool answer_other, uint32_t *zlist, uint32_t *zcount, uint32_t *work,
-                               hipStream_t stream, int leave_per_cu = 0);
+                               hipStream_t stream, int leave_per_cu = 0, bool helper = false);
 hipError_t LaunchKafkaInflate(const Batch &B, const uint32_t *zlist, const uint32_t *zcount, uint8_t *region,
                               hipStream_t stream);
 uint32_t KafkaInflateBlocks();
 uint32_t KafkaInflateRegionBytes();
 hipError_t LaunchMemcacheClassify(const Batch &B, const McTables &T, const uint32_t *sel, const uint32_t *sel2,
                                   const uint32_t *sel_count, bool answer_other, uint32_t scratch_lanes,
-                                  hipStream_t stream, const CopyIn *ci = nullptr);
+                                  hipStream_t stream, const CopyIn *ci = nullptr, int beside_slots = 0,
+                                  uint32_t *work = nullptr);
 hipError_t LaunchR2d2Classify(const Batch &B, const R2Tables &T, bool answer_other, uint32_t scratch_lanes,
                               hipStream_t stream);
 size_t CassandraScratchBytes(uint32_t n, bool sessions = false);

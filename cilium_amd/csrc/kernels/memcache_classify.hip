@@ -566,6 +566,11 @@ __device__ __forceinline__ void mc_kinds(const Batch &B, const McTables &T, cons
     }
 }
 
+// set bits of a wave mask below this lane's
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
 // sel: this protocol's request indices (partition_kernel, mixed batches), else
 // requests 0..n-1.  Each wave takes kMcWaveChunk list entries at a time,
 // reads each one's parser from its first byte (a line the classification
@@ -576,10 +581,13 @@ __device__ __forceinline__ void mc_kinds(const Batch &B, const McTables &T, cons
 // (16 bytes), so the classifying lane starts from the rule set and the
 // request's bytes instead of fetching the entry's metadata a second time.
 // Waves never wait for each other (no workgroup barrier).
+// work: the persistent grid's chunk counter (the launcher's call zeroes it):
+// after its first chunk a wave takes whichever chunk is next, so the grid's
+// waves end together; null: a fixed stride.
 template <bool kNfa, bool kLds, int kCh>
 __device__ __forceinline__ void mc_loop(Batch B, McTables T, const uint8_t *images, const uint32_t *__restrict__ sel,
                                         const uint32_t *__restrict__ sel2, const uint32_t *__restrict__ sel_count,
-                                        uint32_t answer_other, uint4 *ent) {
+                                        uint32_t answer_other, uint4 *ent, uint32_t *__restrict__ work = nullptr) {
     const uint32_t n = B.n;
     // sel: sel_count[0] entries from sel's start, sel_count[1] from its end,
     // sel_count[3] from sel2's end (n slots each); null: all n
@@ -595,10 +603,16 @@ __device__ __forceinline__ void mc_loop(Batch B, McTables T, const uint8_t *imag
                                     answer_other);
         return;
     }
-    const uint64_t below = (1ull << lane) - 1;
     uint4 *slot = ent + wave * kMcWaveChunk;
-    for (uint32_t base = (blockIdx.x * kMcWaves + wave) * kMcWaveChunk; base < m;
-         base += gridDim.x * kMcWaves * kMcWaveChunk) {
+    const uint32_t sweep = gridDim.x * kMcWaves * kMcWaveChunk;
+    auto next_chunk = [&](uint32_t base) -> uint32_t {
+        if (!work) return base + sweep;
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(work, kMcWaveChunk);
+        t = __builtin_amdgcn_readfirstlane(t);
+        return (uint64_t)sweep + t < m ? sweep + t : m;  // (no wrap of the sum, nor of t: below m + one chunk per wave)
+    };
+    for (uint32_t base = (blockIdx.x * kMcWaves + wave) * kMcWaveChunk; base < m; base = next_chunk(base)) {
         uint32_t ix[kMcSortPer], kd[kMcSortPer], ln[kMcSortPer], rsf[kMcSortPer];
         uint64_t of[kMcSortPer];
 #pragma unroll
@@ -617,7 +631,7 @@ __device__ __forceinline__ void mc_loop(Batch B, McTables T, const uint8_t *imag
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const uint64_t mk = __ballot(kd[r] == (uint32_t)k);
-                if (kd[r] == (uint32_t)k) slot[lo[k] + __popcll(mk & below)] = make_uint4(ix[r], ln[r], (uint32_t)of[r], rsf[r]);
+                if (kd[r] == (uint32_t)k) slot[lo[k] + lanes_below(mk)] = make_uint4(ix[r], ln[r], (uint32_t)of[r], rsf[r]);
                 lo[k] += __popcll(mk);
             }
         }
@@ -651,7 +665,8 @@ __device__ __forceinline__ void mc_stage_images(const McTables &T, uint8_t *lds)
     uint4 t[kIters];
 #pragma unroll
     for (uint32_t k = 0; k < kIters; k++)
-        if (threadIdx.x + k * kBlock < n16) t[k] = ((const uint4 *)T.images)[threadIdx.x + k * kBlock];
+        t[k] = threadIdx.x + k * kBlock < n16 ? ((const uint4 *)T.images)[threadIdx.x + k * kBlock]
+                                              : make_uint4(0, 0, 0, 0);  // (every element defined: t stays in registers)
 #pragma unroll
     for (uint32_t k = 0; k < kIters; k++)
         if (threadIdx.x + k * kBlock < n16) ((uint4 *)lds)[threadIdx.x + k * kBlock] = t[k];
@@ -659,20 +674,24 @@ __device__ __forceinline__ void mc_stage_images(const McTables &T, uint8_t *lds)
 }
 __device__ __forceinline__ bool mc_images_fit(const McTables &T) { return T.images_len && T.images_len <= kMcLdsImages; }
 
+// work: mc_loop's.  prio: the wave priority the kernel runs at (0: as launched).
 template <bool kNfa, int kCh>
 __device__ __forceinline__ void mc_classify(Batch B, McTables T, const uint32_t *__restrict__ sel,
                                             const uint32_t *__restrict__ sel2, const uint32_t *__restrict__ sel_count,
-                                            uint32_t answer_other, const CopyIn &ci) {
-    copy_in_block(ci);  // (a one-workgroup call's inputs, when the host asks)
+                                            uint32_t answer_other, uint32_t *__restrict__ work = nullptr,
+                                            uint32_t prio = 0) {
+    // (the instruction takes the level as an immediate)
+    if (prio == 1) __builtin_amdgcn_s_setprio(1);
+    else if (prio == 2) __builtin_amdgcn_s_setprio(2);
+    else if (prio >= 3) __builtin_amdgcn_s_setprio(3);
     extern __shared__ __attribute__((aligned(16))) uint8_t mc_lds[];
     __shared__ uint4 s_ent[kMcWaves][kMcWaveChunk];  // each wave's entries in parser order, with their fields
     if (mc_images_fit(T)) {
         mc_stage_images(T, mc_lds);
-        mc_loop<kNfa, true, kCh>(B, T, mc_lds, sel, sel2, sel_count, answer_other, &s_ent[0][0]);
+        mc_loop<kNfa, true, kCh>(B, T, mc_lds, sel, sel2, sel_count, answer_other, &s_ent[0][0], work);
     } else {
-        mc_loop<kNfa, false, kCh>(B, T, T.images, sel, sel2, sel_count, answer_other, &s_ent[0][0]);
+        mc_loop<kNfa, false, kCh>(B, T, T.images, sel, sel2, sel_count, answer_other, &s_ent[0][0], work);
     }
-    signal_done_block(ci);
 }
 
 // The resident service (kernels/service.h) for the synchronous memcached calls
@@ -722,21 +741,61 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kCh == 1
                                                                                   const uint32_t *__restrict__ sel,
                                                                                   const uint32_t *__restrict__ sel2,
                                                                                   const uint32_t *__restrict__ sel_count,
-                                                                                  uint32_t answer_other, CopyIn ci) {
-    mc_classify<false, kCh>(B, T, sel, sel2, sel_count, answer_other, ci);
+                                                                                  uint32_t answer_other,
+                                                                                  uint32_t *__restrict__ work,
+                                                                                  uint32_t prio) {
+    mc_classify<false, kCh>(B, T, sel, sel2, sel_count, answer_other, work, prio);
 }
 __global__ __launch_bounds__(kBlock) void memcache_classify_nfa_kernel(Batch B, McTables T,
                                                                        const uint32_t *__restrict__ sel,
                                                                        const uint32_t *__restrict__ sel2,
                                                                        const uint32_t *__restrict__ sel_count,
-                                                                       uint32_t answer_other, CopyIn ci) {
-    mc_classify<true, kMcMaxChunks>(B, T, sel, sel2, sel_count, answer_other, ci);
+                                                                       uint32_t answer_other) {
+    mc_classify<true, kMcMaxChunks>(B, T, sel, sel2, sel_count, answer_other);
+}
+// The one-workgroup build of a synchronous call (at most 64 requests): the
+// call's inputs copied in first, when the host asks, and its done word stored
+// last.  The kernels above, which large batches run, carry neither.
+template <bool kNfa, int kCh>
+__global__ __launch_bounds__(kBlock) void memcache_classify_sync_kernel(Batch B, McTables T,
+                                                                        const uint32_t *__restrict__ sel,
+                                                                        const uint32_t *__restrict__ sel2,
+                                                                        const uint32_t *__restrict__ sel_count,
+                                                                        uint32_t answer_other, CopyIn ci) {
+    copy_in_block(ci);
+    mc_classify<kNfa, kCh>(B, T, sel, sel2, sel_count, answer_other);
+    signal_done_block(ci);
 }
 
+// workgroups the device holds at once in `per_cu` slots per CU
+static uint32_t BesideBlocks(int per_cu) {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, c = 0;
+        cus = hipGetDevice(&dev) == hipSuccess &&
+                      hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && c > 0
+                  ? c
+                  : 256;
+    }
+    return (uint32_t)(cus * per_cu);
+}
+
+// Beside Kafka the kernel runs at wave priority 3, as a persistent grid (other
+// values in variant builds, for A/B; profiles/beside_leg/ab_variants_visit*.txt)
+#ifndef L7G_MC_BESIDE_PRIO
+#define L7G_MC_BESIDE_PRIO 3
+#endif
+#ifndef L7G_MC_BESIDE_PERSIST
+#define L7G_MC_BESIDE_PERSIST 1
+#endif
+
 // scratch_lanes: lanes T.nfa_scratch holds (when it is set)
+// beside_slots > 0: the launch runs beside the Kafka kernel's persistent grid,
+// in that many workgroup slots per CU (LaunchKafkaClassify's leave_per_cu);
+// work: a word the call has zeroed, for the chunk counter of a persistent grid
 hipError_t LaunchMemcacheClassify(const Batch &B, const McTables &T, const uint32_t *sel, const uint32_t *sel2,
                                   const uint32_t *sel_count, bool answer_other, uint32_t scratch_lanes,
-                                  hipStream_t stream, const CopyIn *ci) {
+                                  hipStream_t stream, const CopyIn *ci, int beside_slots, uint32_t *work) {
     if (B.n == 0) return hipSuccess;
     // (cfg5, 20M entries: caps of 2048 / 4096 / 8192 / 16384 / 32768 / 131072
     // workgroups -> 3.62 / 3.39 / 3.26 / 3.21 / 3.25 / 3.72 ms; profiles/r5/ab5l_*)
@@ -744,17 +803,37 @@ hipError_t LaunchMemcacheClassify(const Batch &B, const McTables &T, const uint3
     if (blocks > 16384) blocks = 16384;
     if (T.nfa_scratch) blocks = max(1u, min(blocks, scratch_lanes / kBlock));  // (grid-stride loop)
     if (ci && blocks != 1) return hipErrorInvalidValue;  // (the copy is one workgroup's)
-    const CopyIn c = ci ? *ci : CopyIn{};
     const size_t lds = T.images_len && T.images_len <= kMcLdsImages ? ((T.images_len + 15) & ~15u) : 0;
+    const uint32_t other = answer_other ? 1u : 0u;
+    if (ci) {
+        if (T.nfa_pool)
+            hipLaunchKernelGGL((memcache_classify_sync_kernel<true, kMcMaxChunks>), dim3(1), dim3(kBlock), lds, stream, B, T,
+                               sel, sel2, sel_count, other, *ci);
+        else if (T.max_chunks <= 1)
+            hipLaunchKernelGGL((memcache_classify_sync_kernel<false, 1>), dim3(1), dim3(kBlock), lds, stream, B, T, sel, sel2,
+                               sel_count, other, *ci);
+        else
+            hipLaunchKernelGGL((memcache_classify_sync_kernel<false, kMcMaxChunks>), dim3(1), dim3(kBlock), lds, stream, B, T,
+                               sel, sel2, sel_count, other, *ci);
+        return hipGetLastError();
+    }
+    // beside Kafka: the wave priority, and the grid (persistent: one workgroup per slot left)
+    const bool beside = beside_slots > 0 && !T.nfa_pool;
+    const uint32_t prio = beside ? L7G_MC_BESIDE_PRIO : 0;
+    uint32_t *wk = nullptr;
+    if (beside && L7G_MC_BESIDE_PERSIST && work && blocks > BesideBlocks(beside_slots)) {
+        blocks = BesideBlocks(beside_slots);
+        wk = work;
+    }
     if (T.nfa_pool)
         hipLaunchKernelGGL(memcache_classify_nfa_kernel, dim3(blocks), dim3(kBlock), lds, stream, B, T, sel, sel2, sel_count,
-                           answer_other ? 1u : 0u, c);
+                           other);
     else if (T.max_chunks <= 1)
         hipLaunchKernelGGL(memcache_classify_kernel<1>, dim3(blocks), dim3(kBlock), lds, stream, B, T, sel, sel2, sel_count,
-                           answer_other ? 1u : 0u, c);
+                           other, wk, prio);
     else
         hipLaunchKernelGGL(memcache_classify_kernel<kMcMaxChunks>, dim3(blocks), dim3(kBlock), lds, stream, B, T, sel, sel2,
-                           sel_count, answer_other ? 1u : 0u, c);
+                           sel_count, other, wk, prio);
     return hipGetLastError();
 }
 
