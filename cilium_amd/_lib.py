@@ -45,12 +45,45 @@ EXPORTS = (
     "l7g_frame_streams", "l7g_classify_streams", "l7g_service_enable", "l7g_service_stats",
     "l7g_cass_sessions_enable", "l7g_cass_replies", "l7g_cass_replies_host", "l7g_cass_session_reset",
     "l7g_cass_session_stats",
+    "l7g_classify_logged", "l7g_classify_logged_host", "l7g_kafka_api_key_name",
 )
 
 
 class FlowStat(C.Structure):
     _fields_ = [("policy", C.c_int32), ("proto", C.c_uint8), ("ingress", C.c_uint8), ("port", C.c_uint16),
                 ("received", C.c_uint64), ("forwarded", C.c_uint64), ("denied", C.c_uint64), ("error", C.c_uint64)]
+
+
+class Span(C.Structure):
+    """l7g_span_t: bytes from the request's first byte."""
+    _fields_ = [("off", C.c_uint32), ("len", C.c_uint32)]
+
+
+class _LogHttp(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("method_len", "path_len", "host_off", "host_len", "head_len", "nheaders")]
+
+
+class _LogKafka(C.Structure):
+    _fields_ = [("api_version", C.c_int16), ("pad", C.c_int16), ("correlation_id", C.c_int32),
+                ("ntopics", C.c_uint32)]
+
+
+class _LogUnion(C.Union):
+    _fields_ = [("http", _LogHttp), ("kafka", _LogKafka)]
+
+
+class LogRec(C.Structure):
+    """l7g_logrec_t (32 bytes): one access-log record per request."""
+    _fields_ = [("kind", C.c_uint8), ("flags", C.c_uint8), ("api_key", C.c_int16), ("u", _LogUnion),
+                ("reserved", C.c_uint32)]
+
+
+class LogOut(C.Structure):
+    """l7g_log_out_t."""
+    _fields_ = [("rec", C.c_void_p), ("topics", C.c_void_p), ("topic_stride", C.c_uint32)]
+
+
+LOG_NONE, LOG_HTTP, LOG_KAFKA = 0, 1, 2
 
 _libs = {}
 
@@ -122,6 +155,16 @@ def load(path=None):
     lib.l7g_flow_stats_enable.argtypes = [vp, C.c_int]
     lib.l7g_flow_stats.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.c_int]
     lib.l7g_profile_last.argtypes = [vp, vp]
+    # (a library named by L7G_LIB or by path may be an earlier build without the logged calls, as in an
+    # A/B against the parent commit's: it loads, and calling them raises AttributeError.  libl7gpu.so
+    # has them: tests/test_access_log_abi.py)
+    if hasattr(lib, "l7g_classify_logged"):
+        lib.l7g_classify_logged.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp, vp,
+                                            C.POINTER(LogOut), vp]
+        lib.l7g_classify_logged_host.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp,
+                                                 C.POINTER(LogOut)]
+        lib.l7g_kafka_api_key_name.restype = cp
+        lib.l7g_kafka_api_key_name.argtypes = [C.c_int16]
     _libs[path] = lib
     return lib
 
@@ -140,6 +183,13 @@ def debug_regex(pattern, data, anchored=True, nfa=False):
     if r < 0:
         raise ValueError(err.value.decode(errors="replace"))
     return bool(r)
+
+
+def kafka_api_key_name(key):
+    """The policy language's name of a Kafka API key (apiKeyToString), or None
+    for a key it does not name (print that one in decimal)."""
+    r = load().l7g_kafka_api_key_name(int(key))
+    return r.decode() if r is not None else None
 
 
 def kafka_deny_response(req):

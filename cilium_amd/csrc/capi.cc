@@ -585,6 +585,17 @@ void l7g_cass_session_stats(l7g_engine *e, uint64_t out[6]) {
     out[5] = h[CSS_UNPREPARED];
 }
 
+// the access-log record's layout as the kernels write it (LogRec / LogSpan, device_tables.h)
+static_assert(sizeof(l7g_logrec_t) == 32 && sizeof(LogRec) == 32 && sizeof(l7g_span_t) == 8 && sizeof(LogSpan) == 8,
+              "record and span sizes");
+static_assert(offsetof(l7g_logrec_t, api_key) == 2 && offsetof(l7g_logrec_t, u.http.method_len) == 4 &&
+                  offsetof(l7g_logrec_t, u.http.nheaders) == 24 && offsetof(l7g_logrec_t, u.kafka.api_version) == 4 &&
+                  offsetof(l7g_logrec_t, u.kafka.correlation_id) == 8 && offsetof(l7g_logrec_t, u.kafka.ntopics) == 12,
+              "record fields");
+static_assert(L7G_LOG_HTTP == LOG_HTTP && L7G_LOG_KAFKA == LOG_KAFKA, "record kinds");
+
+const char *l7g_kafka_api_key_name(int16_t key) { return KafkaApiKeyName(key); }
+
 int l7g_stats(l7g_engine *e, l7g_stats_t *out) {
     std::lock_guard<std::mutex> g(e->mu);
     memset(out, 0, sizeof *out);

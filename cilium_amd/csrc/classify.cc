@@ -65,11 +65,16 @@ static hipError_t GetScratch(l7g_engine *e, hipStream_t s, StreamScratch **out) 
 // pre: the call's inputs still to be copied from pinned host memory to where
 // arena / off / len / conn point (HostRun); done by the first kernel when the
 // call is one workgroup of one classifier, else by copy_in_kernel first.
+// log: l7g_classify_logged's outputs (device memory).  The plan is the same;
+// the Kafka grids are the logged instantiations, and http_log_kernel follows
+// the classifiers (it reads their verdicts).
 int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
              const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed, uint64_t *counters,
-             void *stream, const uint32_t *host_conn, const CopyIn *pre, bool *signaled) {
+             void *stream, const uint32_t *host_conn, const CopyIn *pre, bool *signaled, const LogOut *log) {
     std::lock_guard<std::mutex> g(e->mu);
     if (e->device < 0) return (int)hipErrorNoDevice;
+    if (log && (!log->rec || ((uintptr_t)log->rec & 15) || (log->stride && !log->topics) || pre))
+        return (int)hipErrorInvalidValue;
     hipError_t rc = hipSetDevice(e->device);
     if (rc == hipSuccess) rc = Upload(e);
     if (rc == hipSuccess) rc = SessionsSync(e);
@@ -242,7 +247,7 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
     uint32_t *zcount = cnt ? cnt + kCntKafkaZ : nullptr;
     if (rc == hipSuccess && run[2])
         rc = LaunchKafkaClassify(B, e->kt, sel_k, cnt, !partitioned, sel_z, zcount, cnt ? cnt + kCntKafkaWork : nullptr,
-                                 s, kafka_leave);
+                                 s, kafka_leave, false, log);
     // requests with gzip / snappy messages: decoded, their sets read, failures answered
     auto inflate = [&]() {
         if (rc != hipSuccess || !run[2] || !sel_z) return;
@@ -265,7 +270,7 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
         // (cfg5: 33.46 -> 33.10 ms per step, profiles/beside_leg/ab_variants_visit2.txt)
         if (L7G_KAFKA_HELPER)
             rc = LaunchKafkaClassify(B, e->kt, sel_k, cnt, !partitioned, sel_z, zcount, cnt + kCntKafkaWork, ms,
-                                     kafka_leave, true);
+                                     kafka_leave, true, log);
         if (rc == hipSuccess) rc = hipEventRecord(S->join_ev, ms);
         if (rc == hipSuccess) rc = hipStreamWaitEvent(s, S->join_ev, 0);
         inflate();
@@ -285,6 +290,8 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
             rc = LaunchCassandraClassify(B, ct, S->d_use, S->use_cap, !partitioned, big_lanes, s);
     }
     mark(4);
+    // access-log records: every request's but Kafka's (written above), from the verdicts
+    if (rc == hipSuccess && log) rc = LaunchHttpLog(B, log->rec, s);
     // proxy statistics (accumulated on the device until read)
     if (rc == hipSuccess && e->flow_stats && !e->skey_list.empty()) {
         const size_t nk = e->skey_list.size();
@@ -354,6 +361,15 @@ int l7g_classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const 
                  const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed,
                  uint64_t *counters, void *stream) {
     return Classify(e, arena, arena_len, off, len, conn, n, verdict, rule, consumed, counters, stream, nullptr);
+}
+
+int l7g_classify_logged(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                        const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule,
+                        uint32_t *consumed, uint64_t *counters, const l7g_log_out_t *log, void *stream) {
+    if (!log) return (int)hipErrorInvalidValue;
+    const LogOut lo{reinterpret_cast<LogRec *>(log->rec), reinterpret_cast<LogSpan *>(log->topics), log->topic_stride};
+    return Classify(e, arena, arena_len, off, len, conn, n, verdict, rule, consumed, counters, stream, nullptr, nullptr,
+                    nullptr, &lo);
 }
 
 int l7g_frame_streams(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *s_off,

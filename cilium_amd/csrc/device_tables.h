@@ -71,6 +71,21 @@ struct Batch {
     uint32_t n, nconns;
 };
 
+// The access-log outputs of a logged call (l7g_log_out_t, include/l7gpu.h):
+// one 32-byte record per request, written as two 16-byte stores, and a row of
+// `stride` topic-name spans per request.  Word 0 of a record is
+// kind | flags << 8 | api_key << 16; HTTP: words 1-6 method_len, path_len,
+// host_off, host_len, head_len, nheaders; Kafka: word 1 api_version, word 2
+// correlation id, word 3 ntopics.
+enum : uint32_t { LOG_NONE = 0, LOG_HTTP = 1, LOG_KAFKA = 2 };
+struct alignas(16) LogRec { uint32_t w[8]; };
+struct LogSpan { uint32_t off, len; };
+struct LogOut {
+    LogRec *rec;
+    LogSpan *topics;
+    uint32_t stride;
+};
+
 // A request whose bytes leave [arena, arena + arena_len) is out of contract:
 // every kernel answers it UNSUPPORTED instead of reading past the arena.
 L7_HD inline bool l7_in_arena(uint64_t off, uint32_t len, uint64_t arena_len) {

@@ -123,8 +123,13 @@ struct HostCtx {
     uint32_t *pin_done_dev = nullptr;
     uint32_t seq = 0;
     size_t in_cap = 0, out_cap = 0;
+    // l7g_classify_logged_host: [records | topic rows], on the device and pinned (grow-only)
+    uint8_t *log_dev = nullptr, *log_pin = nullptr;
+    size_t log_cap = 0;
     ~HostCtx() {
         if (s) hipStreamSynchronize(s);
+        if (log_dev) hipFree(log_dev);
+        if (log_pin) hipHostFree(log_pin);
         if (dev) hipFree(dev);
         if (pin_in) hipHostFree(pin_in);
         if (pin_out) hipHostFree(pin_out);
@@ -298,7 +303,8 @@ int CassReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const u
                 const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream);
 int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
              const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed, uint64_t *counters,
-             void *stream, const uint32_t *host_conn, const CopyIn *pre = nullptr, bool *signaled = nullptr);
+             void *stream, const uint32_t *host_conn, const CopyIn *pre = nullptr, bool *signaled = nullptr,
+             const LogOut *log = nullptr);
 void StopServices(l7g_engine *e);  // service.cc, as the next two
 void ReleaseServiceCUs(l7g_engine *e);
 bool ServiceTry(l7g_engine *e, uint32_t n, uint64_t arena_len, const HostIn &in, uint8_t *verdict, int32_t *rule,

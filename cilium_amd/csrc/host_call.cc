@@ -274,6 +274,67 @@ int l7g_classify_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, c
     return HostRunStaged(e, n, arena_len, verdict, rule, consumed, false);
 }
 
+// l7g_classify_host with the access-log outputs: the calling thread's stream
+// and staging, one copy in, the launch plan of Classify with the log outputs
+// (always launched: no resident service, no zero-copy), the outputs, records
+// and topic rows copied out, a wait.  The caller's topic rows go in first, so
+// that the rows no kernel writes (requests that are not Kafka) come back as
+// they were.
+int l7g_classify_logged_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                             const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule,
+                             uint32_t *consumed, const l7g_log_out_t *log) {
+    if (!log || !log->rec || (log->topic_stride && !log->topics)) return (int)hipErrorInvalidValue;
+    uint8_t *pa;
+    uint64_t *po;
+    uint32_t *pl, *pc;
+    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
+    if (rc0 != 0 || n == 0) return rc0;
+    memcpy(po, off, (size_t)n * 8);
+    memcpy(pl, len, (size_t)n * 4);
+    memcpy(pc, conn, (size_t)n * 4);
+    if (arena_len) memcpy(pa, arena, arena_len);
+    HostCtx *H = nullptr;
+    hipError_t rc = HostEnter(e, &H);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t rec_b = (size_t)n * sizeof(l7g_logrec_t);
+    const size_t top_b = (size_t)n * log->topic_stride * sizeof(l7g_span_t);
+    if (rec_b + top_b > H->log_cap) {
+        hipStreamSynchronize(H->s);
+        if (H->log_dev) hipFree(H->log_dev);
+        if (H->log_pin) hipHostFree(H->log_pin);
+        H->log_dev = H->log_pin = nullptr;
+        H->log_cap = 0;
+        const size_t cap = rec_b + top_b + (rec_b + top_b) / 4;
+        if ((rc = hipMalloc(&H->log_dev, cap)) != hipSuccess) return (int)rc;
+        if ((rc = hipHostMalloc(&H->log_pin, cap, hipHostMallocDefault)) != hipSuccess) return (int)rc;
+        H->log_cap = cap;
+    }
+    const size_t nn = CallNn(n);
+    uint8_t *d_in = H->dev, *d_out = H->dev + H->in_cap;
+    const LogOut lo{(LogRec *)H->log_dev, top_b ? (LogSpan *)(H->log_dev + rec_b) : nullptr, log->topic_stride};
+    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
+    if (rc == hipSuccess && top_b) {
+        memcpy(H->log_pin + rec_b, log->topics, top_b);
+        rc = hipMemcpyAsync(H->log_dev + rec_b, H->log_pin + rec_b, top_b, hipMemcpyHostToDevice, H->s);
+    }
+    if (rc == hipSuccess)
+        rc = (hipError_t)Classify(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
+                                  (const uint32_t *)(d_in + CallLenOff(nn)), (const uint32_t *)(d_in + CallConnOff(nn)),
+                                  n, d_out, (int32_t *)(d_out + CallRuleOff(n)), (uint32_t *)(d_out + CallConsumedOff(n)),
+                                  nullptr, H->s, pc, nullptr, nullptr, &lo);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(H->pin_out, d_out, CallOutBytes(n), hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(H->log_pin, H->log_dev, rec_b + top_b, hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
+    if (rc == hipSuccess) {
+        memcpy(verdict, H->pin_out, n);
+        memcpy(rule, H->pin_out + CallRuleOff(n), (size_t)n * 4);
+        memcpy(consumed, H->pin_out + CallConsumedOff(n), (size_t)n * 4);
+        memcpy(log->rec, H->log_pin, rec_b);
+        if (top_b) memcpy(log->topics, H->log_pin + rec_b, top_b);
+    }
+    return (int)rc;
+}
+
 // l7g_cass_replies with host buffers, over the calling thread's stream and
 // staging: one copy in, the reply kernels, one copy out, a wait.
 int l7g_cass_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,

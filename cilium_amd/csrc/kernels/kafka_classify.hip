@@ -555,6 +555,14 @@ __device__ __forceinline__ uint32_t matches_rule(const KafkaTables &T, const Dev
 }
 
 // ---------------- the lane-serial classification ----------------
+// What the hooks keep for the access log (l7g_classify_logged): nothing, or the
+// request's row of topic-name spans.
+struct NoTopicLog {};
+struct TopicLog {
+    LogSpan *row;
+    uint32_t stride;
+};
+template <class L>
 struct ExactHooks {
     const KafkaTables &T;
     const DevKafkaRuleset &rs;
@@ -563,12 +571,17 @@ struct ExactHooks {
     const uint32_t *crctab;
     uint8_t *stage;
     uint32_t ntopics, cmax;
+    L log;
     __device__ __forceinline__ void client(uint32_t o, uint32_t l) {
         q.client = str_lookup(T.client_hash, T.client_mask, T.strings, r, o, l);
         if (q.client < 0) q.client = -2;
     }
     __device__ __forceinline__ void topic(uint32_t o, uint32_t l) {
         if (q.typed != 1) return;
+        if constexpr (!std::is_same<L, NoTopicLog>::value) {
+            // GetTopics(): every topic in wire order, duplicates kept; the row holds the first `stride`
+            if (ntopics < log.stride) log.row[ntopics] = LogSpan{o, l};
+        }
         ntopics++;
         const int32_t tid = l > 0 ? str_lookup(T.topic_hash, T.topic_mask, T.strings, r, o, l) : -1;
         const uint32_t e = topic_first(T, rs, q, tid);
@@ -594,11 +607,19 @@ struct ExactHooks {
 // beside it in the workgroup slot it leaves per CU, 5 (96 VGPRs, almost no
 // spills) when it runs alone (cfg3 0.619 -> 0.601 ms; beside memcached the
 // 5-wave build loses: profiles/r6/ab6za_*).
-template <int kWaves>
+// kLog (l7g_classify_logged): the same classification, and beside each ALLOW /
+// DENY verdict the request's access-log record (LogRec, device_tables.h) and,
+// from the topic hook, the first lstride topic-name spans into its row of
+// ltopics.  Where a produce request's later topics begin depends on its
+// messages' CRCs (a message set that stops without draining), so the spans come
+// from this walk, not from a second pass.  The unlogged instantiations ignore
+// the last three arguments.  The logged one is built for 4 waves per SIMD, where
+// the extra live values (row pointer, stride, record words) fit without spills.
+template <int kWaves, bool kLog>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 8))) void kafka_classify_kernel(
     Batch B, KafkaTables T, const uint32_t *__restrict__ sel, const uint32_t *__restrict__ sel_count,
     uint32_t answer_other, uint32_t *__restrict__ zlist, uint32_t *__restrict__ zcount, uint32_t *__restrict__ work,
-    uint32_t main_sweep) {
+    uint32_t main_sweep, LogRec *__restrict__ lrec, LogSpan *__restrict__ ltopics, uint32_t lstride) {
     const uint32_t n = B.n, nconns = B.nconns;
     static_assert(kBlock >= 256, "one CRC table entry per thread");
     __shared__ uint32_t crctab[kCrcTables * 256];
@@ -684,10 +705,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
             q.client = -2;
             // fields are read where they are used: a copy would hold 9 VGPRs across the decode
             const DevKafkaRuleset &rs = T.rulesets[conn.ruleset];
-            ExactHooks h{T, rs, q, r, crctab, stage, 0, 0};
+            using Log = typename std::conditional<kLog, TopicLog, NoTopicLog>::type;
+            Log lg{};
+            if constexpr (kLog) lg = TopicLog{ltopics + (size_t)idx * lstride, lstride};
+            ExactHooks<Log> h{T, rs, q, r, crctab, stage, 0, 0, lg};
             if (q.typed && kafka_walk(r, rawlen, q.kind, zflag, h) == -1) break;
             consumed = rawlen;
             verdict = V_DENY;
+            if constexpr (kLog) {
+                const uint32_t corr = (uint32_t)r.be(8, 4);  // (rawlen >= 12)
+                uint4 *o = reinterpret_cast<uint4 *>(lrec + idx);
+                o[0] = make_uint4(LOG_KAFKA | (h.ntopics > lstride ? 0x100u : 0u) | ((uint32_t)(uint16_t)q.kind << 16),
+                                  (uint32_t)(uint16_t)q.version, corr, h.ntopics);
+                o[1] = make_uint4(0, 0, 0, 0);
+            }
             if (!rs.any) break;
             const uint32_t best = matches_rule(T, rs, q, h.ntopics, h.cmax);
             if (best != kInf) { verdict = V_ALLOW; rule = T.rules[rs.rule_first + best].gid; }
@@ -705,44 +736,44 @@ hipError_t KafkaPhaseTimes(uint64_t *, bool) { return hipErrorNotSupported; }
 // free for a kernel running beside this one on another stream
 // helper (with leave_per_cu > 0 and a counter): not the main grid but a second, small one for the slots
 // the main grid left, launched behind the kernel that ran in them; it draws from the same counter
+// log (l7g_classify_logged): the logged instantiations, which also write the records and topic rows
 hipError_t LaunchKafkaClassify(const Batch &B, const KafkaTables &T, const uint32_t *sel, const uint32_t *sel_count,
                                bool answer_other, uint32_t *zlist, uint32_t *zcount, uint32_t *work,
-                               hipStream_t stream, int leave_per_cu, bool helper) {
+                               hipStream_t stream, int leave_per_cu, bool helper, const LogOut *log) {
     if (B.n == 0) return hipSuccess;
     uint32_t blocks = (B.n + kBlock - 1) / kBlock;
     const bool beside = leave_per_cu > 0;
     if (helper && (!beside || !work)) return hipErrorInvalidValue;
+    const bool lg = log != nullptr;
+    // (logged: one build for both places, the 4-wave one -- 118 VGPRs, no spill and no scratch, where
+    // the 5-wave build spills 21 VGPRs and the 6-wave one 37; profiles/access_log/kernel_resources.txt)
+    const auto kernel = lg ? kafka_classify_kernel<4, true>
+                           : (beside ? kafka_classify_kernel<6, false> : kafka_classify_kernel<5, false>);
     // persistent grid: as many workgroups as the CUs hold at once (per build)
-    static int cus[2] = {0, 0}, per_cu[2] = {0, 0};
-    if (cus[beside] == 0) {
+    static int cus[2][2] = {}, per_cu[2][2] = {};
+    if (cus[lg][beside] == 0) {
         int dev = 0, c = 0, p = 0;
         if (hipGetDevice(&dev) == hipSuccess &&
             hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &p, beside ? kafka_classify_kernel<6> : kafka_classify_kernel<5>, kBlock, 0) == hipSuccess &&
-            c > 0 && p > 0) {
-            per_cu[beside] = p;
-            cus[beside] = c;
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, kernel, kBlock, 0) == hipSuccess && c > 0 && p > 0) {
+            per_cu[lg][beside] = p;
+            cus[lg][beside] = c;
         } else {
-            per_cu[beside] = 32;
-            cus[beside] = 256;
+            per_cu[lg][beside] = 32;
+            cus[lg][beside] = 256;
         }
     }
-    const int pc = per_cu[beside];
+    const int pc = per_cu[lg][beside], ncu = cus[lg][beside];
     const int slots = beside && pc > leave_per_cu ? pc - leave_per_cu : pc;
     if (!work) blocks = blocks > 8192 ? 8192 : blocks;  // grid-stride beyond this
-    else if (blocks > (uint32_t)(cus[beside] * slots)) blocks = (uint32_t)(cus[beside] * slots);
-    if (helper) {
-        // (blocks: the main grid's, as its launch computed them)
-        const uint32_t mine = min(blocks, (uint32_t)(cus[beside] * min(leave_per_cu, pc)));
-        hipLaunchKernelGGL(kafka_classify_kernel<6>, dim3(mine), dim3(kBlock), 0, stream, B, T, sel, sel_count,
-                           answer_other ? 1u : 0u, zlist, zcount, work, blocks * (uint32_t)kBlock);
-    } else if (beside)
-        hipLaunchKernelGGL(kafka_classify_kernel<6>, dim3(blocks), dim3(kBlock), 0, stream, B, T, sel, sel_count,
-                           answer_other ? 1u : 0u, zlist, zcount, work, 0u);
-    else
-        hipLaunchKernelGGL(kafka_classify_kernel<5>, dim3(blocks), dim3(kBlock), 0, stream, B, T, sel, sel_count,
-                           answer_other ? 1u : 0u, zlist, zcount, work, 0u);
+    else if (blocks > (uint32_t)(ncu * slots)) blocks = (uint32_t)(ncu * slots);
+    // (helper: blocks is the main grid's, as its launch computed them)
+    const uint32_t grid = helper ? min(blocks, (uint32_t)(ncu * min(leave_per_cu, pc))) : blocks;
+    const uint32_t main_sweep = helper ? blocks * (uint32_t)kBlock : 0u;
+    LogRec *lrec = lg ? log->rec : nullptr;
+    LogSpan *ltopics = lg ? log->topics : nullptr;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, B, T, sel, sel_count, answer_other ? 1u : 0u, zlist,
+                       zcount, work, main_sweep, lrec, ltopics, lg ? log->stride : 0u);
     return hipGetLastError();
 }
 

@@ -15,7 +15,10 @@ hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const uint32_
                               hipStream_t stream);
 hipError_t LaunchKafkaClassify(const Batch &B, const KafkaTables &T, const uint32_t *sel, const uint32_t *sel_count,
                                bool answer_other, uint32_t *zlist, uint32_t *zcount, uint32_t *work,
-                               hipStream_t stream, int leave_per_cu = 0, bool helper = false);
+                               hipStream_t stream, int leave_per_cu = 0, bool helper = false,
+                               const LogOut *log = nullptr);
+// the logged calls' post-pass (kernels/http_log.hip): the records of every request but Kafka's
+hipError_t LaunchHttpLog(const Batch &B, LogRec *rec, hipStream_t stream);
 hipError_t LaunchKafkaInflate(const Batch &B, const uint32_t *zlist, const uint32_t *zcount, uint8_t *region,
                               hipStream_t stream);
 uint32_t KafkaInflateBlocks();

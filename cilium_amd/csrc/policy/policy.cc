@@ -53,6 +53,19 @@ void NetworkPolicy::Lookup(bool in, uint32_t port, const PortPolicy **exact, con
     }
 }
 
+// KafkaAPIKeyMap (pkg/policy/api/kafka.go:153-197), by API key
+static const char *const kKeys[] = {
+    "produce", "fetch", "offsets", "metadata", "leaderandisr", "stopreplica", "updatemetadata",
+    "controlledshutdown", "offsetcommit", "offsetfetch", "findcoordinator", "joingroup", "heartbeat",
+    "leavegroup", "syncgroup", "describegroups", "listgroups", "saslhandshake", "apiversions",
+    "createtopics", "deletetopics", "deleterecords", "initproducerid", "offsetforleaderepoch",
+    "addpartitionstotxn", "addoffsetstotxn", "endtxn", "writetxnmarkers", "txnoffsetcommit",
+    "describeacls", "createacls", "deleteacls", "describeconfigs", "alterconfigs"};
+
+const char *KafkaApiKeyName(int key) {
+    return key >= 0 && key < (int)(sizeof kKeys / sizeof kKeys[0]) ? kKeys[key] : nullptr;
+}
+
 namespace {
 
 using json::Value;
@@ -133,13 +146,6 @@ struct Loader {
     }
 
     bool kafka(const Value &j, KafkaRule *k) {
-        static const char *kKeys[] = {
-            "produce", "fetch", "offsets", "metadata", "leaderandisr", "stopreplica", "updatemetadata",
-            "controlledshutdown", "offsetcommit", "offsetfetch", "findcoordinator", "joingroup", "heartbeat",
-            "leavegroup", "syncgroup", "describegroups", "listgroups", "saslhandshake", "apiversions",
-            "createtopics", "deletetopics", "deleterecords", "initproducerid", "offsetforleaderepoch",
-            "addpartitionstotxn", "addoffsetstotxn", "endtxn", "writetxnmarkers", "txnoffsetcommit",
-            "describeacls", "createacls", "deleteacls", "describeconfigs", "alterconfigs"};
         std::string role, key, ver, s;
         str(j, "role", &role);
         str(j, "apiKey", &key);

@@ -97,6 +97,8 @@ struct PortRule {
 // "r2d2", "cassandra", "test.headerparser", "PortNetworkPolicyRule_HttpRules",
 // "PortNetworkPolicyRule_KafkaRules".
 bool ProxylibParserRegistered(const std::string &name);
+// the policy language's name of a Kafka API key (l7g_kafka_api_key_name), nullptr = none
+const char *KafkaApiKeyName(int key);
 
 struct PortPolicy {
     uint32_t port = 0;

@@ -144,6 +144,49 @@ class Engine:
             raise RuntimeError(f"l7g_classify_host failed: HIP error {rc}")
         return v, r, c
 
+    # ------------------------------------------------------------ access log
+    def classify_logged_device(self, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, verdict_ptr, rule_ptr,
+                               consumed_ptr, records_ptr, topics_ptr=0, topic_stride=0, counters_ptr=0, stream=0):
+        """l7g_classify_logged: classify_device, and one 32-byte record per
+        request at records_ptr (16-byte aligned) plus n rows of topic_stride
+        8-byte spans at topics_ptr; all pointers are device addresses."""
+        lo = _lib.LogOut(records_ptr, topics_ptr or None, topic_stride)
+        rc = self._lib.l7g_classify_logged(self._h, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, verdict_ptr,
+                                           rule_ptr, consumed_ptr, counters_ptr or None, C.byref(lo), stream or None)
+        if rc != 0:
+            raise RuntimeError(f"l7g_classify_logged failed: HIP error {rc}")
+
+    def classify_logged(self, arena, offsets, lengths, conn_ids, topic_stride=4, topics=None):
+        """classify(), with the access-log outputs: returns (verdict, rule,
+        consumed, records, topics).  records is a LOGREC_DTYPE array (read its
+        http_* fields where kind == 1, its kafka_* fields where kind == 2, and
+        only where the verdict is ALLOW or DENY); topics is an (n,
+        topic_stride) SPAN_DTYPE array whose row i holds the first
+        min(ntopics, topic_stride) topic-name spans of Kafka request i.  Rows
+        of other requests are not written: they keep what `topics` held (zeros
+        when not given)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        n = len(off)
+        v = np.zeros(n, np.uint8)
+        r = np.zeros(n, np.int32)
+        c = np.zeros(n, np.uint32)
+        rec = np.zeros(n, LOGREC_DTYPE)
+        if topics is None:
+            topics = np.zeros((n, topic_stride), SPAN_DTYPE)
+        topics = np.ascontiguousarray(topics, dtype=SPAN_DTYPE)
+        if topics.shape != (n, topic_stride):
+            raise ValueError("topics must have shape (n, topic_stride)")
+        lo = _lib.LogOut(rec.ctypes.data, topics.ctypes.data if topic_stride else None, topic_stride)
+        rc = self._lib.l7g_classify_logged_host(self._h, arena.ctypes.data, arena.nbytes, off.ctypes.data,
+                                                ln.ctypes.data, cid.ctypes.data, n, v.ctypes.data, r.ctypes.data,
+                                                c.ctypes.data, C.byref(lo))
+        if rc != 0:
+            raise RuntimeError(f"l7g_classify_logged_host failed: HIP error {rc}")
+        return v, r, c, rec, topics
+
     # ---------------------------------------------------- cassandra sessions
     def cass_sessions(self, max_statements):
         """Device-resident cassandra sessions (l7g_cass_sessions_enable): with
@@ -275,6 +318,17 @@ class Engine:
 CONN_DTYPE = np.dtype([("policy", "<i4"), ("port", "<u4"), ("ingress", "u1"), ("proto", "u1"),
                        ("flags", "<u2"), ("src_id", "<u4"), ("dst_id", "<u4")])
 assert CONN_DTYPE.itemsize == C.sizeof(Conn)
+
+
+# l7g_logrec_t as a numpy record: the union's two views over the same bytes
+LOGREC_DTYPE = np.dtype({
+    "names": ["kind", "flags", "api_key", "method_len", "path_len", "host_off", "host_len", "head_len", "nheaders",
+              "api_version", "correlation_id", "ntopics"],
+    "formats": ["u1", "u1", "<i2", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<i2", "<i4", "<u4"],
+    "offsets": [0, 1, 2, 4, 8, 12, 16, 20, 24, 4, 8, 12],
+    "itemsize": 32})
+SPAN_DTYPE = np.dtype([("off", "<u4"), ("len", "<u4")])
+assert LOGREC_DTYPE.itemsize == C.sizeof(_lib.LogRec) and SPAN_DTYPE.itemsize == C.sizeof(_lib.Span)
 
 
 def conns_array(conns):

@@ -215,6 +215,69 @@ int l7g_classify_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, c
 
 int l7g_stats(l7g_engine *e, l7g_stats_t *out);
 
+/* Access-log records (opt-in; l7g_classify and l7g_classify_host are untouched
+ * by it).  The logged calls classify exactly as the plain ones -- the same
+ * launch plan, verdict / rule / consumed / counters, streams and scratch -- and
+ * also write one fixed-size record per request with the fields the reference's
+ * log entries carry: Envoy's HttpLogEntry (envoy/accesslog.cc:59-133,
+ * InitFromRequest: method, path, host, protocol) and the Kafka proxy's
+ * LogRecordKafka, one per topic (pkg/proxy/kafka.go:169-231,
+ * pkg/proxy/accesslog/record.go:203-245: API key, version, correlation id,
+ * topic).
+ *
+ * rec[i] means something only where verdict[i] is L7G_ALLOW or L7G_DENY; the
+ * verdict array is the authority (a compressed Kafka request can still turn
+ * L7G_PARSE_ERROR after its record was written).  Everywhere else kind and the
+ * rest of rec[i] are unspecified.  Requests on memcached, r2d2 and cassandra
+ * connections get kind 0.
+ *
+ * HTTP (kind 1): the method is request bytes [0, method_len), the path
+ * [method_len + 1, method_len + 1 + path_len); host_off / host_len the value
+ * of the first Host header (name matched without case, optional whitespace
+ * trimmed; flags bit0 = such a header is present, its length 0 for an empty
+ * value); head_len the offset just past the empty line; nheaders the number of
+ * header lines (the caller reads them from [0, head_len)); api_key the
+ * protocol version, (major digit << 4) | minor digit of "HTTP/x.y".
+ *
+ * Kafka (kind 2): api_key, api_version and correlation_id are the big-endian
+ * fields at request bytes 4, 6 and 8 (GetAPIKey, GetVersion,
+ * GetCorrelationID); ntopics the length of GetTopics()
+ * (pkg/kafka/request.go:88-153: every topic in wire order, duplicates kept; 0
+ * for an untyped request, ConsumerMetadata and a null Metadata / OffsetFetch
+ * array).  topics is n rows of topic_stride spans: row i receives the spans
+ * (from the request's first byte; an empty name is {0, 0}) of the first
+ * min(ntopics, topic_stride) topic names; rows of requests that are not Kafka
+ * are never written.  A request with more topics than the stride sets flags
+ * bit0: submit it again, alone, with a stride of its ntopics.  topic_stride 0
+ * with topics NULL is valid.
+ *
+ * rec and topics are device memory for l7g_classify_logged (rec 16-byte
+ * aligned) and host memory for l7g_classify_logged_host, which always launches
+ * (it does not post to a resident service) and gives l7g_classify_host's
+ * verdicts. */
+typedef struct { uint32_t off, len; } l7g_span_t; /* bytes from the request's first byte */
+enum { L7G_LOG_NONE = 0, L7G_LOG_HTTP = 1, L7G_LOG_KAFKA = 2 };
+typedef struct {
+    uint8_t kind;    /* L7G_LOG_* */
+    uint8_t flags;   /* HTTP bit0: a Host header is present.  Kafka bit0: ntopics > topic_stride */
+    int16_t api_key; /* Kafka; HTTP: (major digit << 4) | minor digit */
+    union {
+        struct { uint32_t method_len, path_len, host_off, host_len, head_len, nheaders; } http;
+        struct { int16_t api_version, pad; int32_t correlation_id; uint32_t ntopics; } kafka;
+    } u;
+    uint32_t reserved; /* 0 */
+} l7g_logrec_t; /* 32 bytes */
+typedef struct { l7g_logrec_t *rec; l7g_span_t *topics; uint32_t topic_stride; } l7g_log_out_t;
+int l7g_classify_logged(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                        const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule,
+                        uint32_t *consumed, uint64_t *counters, const l7g_log_out_t *log, void *stream);
+int l7g_classify_logged_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                             const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule,
+                             uint32_t *consumed, const l7g_log_out_t *log);
+/* The API key's name as the policy language spells it (apiKeyToString,
+ * pkg/proxy/kafka.go:162-167); NULL = unknown: print the key in decimal. */
+const char *l7g_kafka_api_key_name(int16_t key);
+
 /* Cassandra sessions (off by default; with them off every answer is the
  * stateless one, byte for byte).
  *
