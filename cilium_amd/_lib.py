@@ -46,6 +46,7 @@ EXPORTS = (
     "l7g_cass_sessions_enable", "l7g_cass_replies", "l7g_cass_replies_host", "l7g_cass_session_reset",
     "l7g_cass_session_stats",
     "l7g_classify_logged", "l7g_classify_logged_host", "l7g_kafka_api_key_name",
+    "l7g_deny_replies", "l7g_deny_replies_host", "l7g_deny_reply_template",
 )
 
 
@@ -84,6 +85,13 @@ class LogOut(C.Structure):
 
 
 LOG_NONE, LOG_HTTP, LOG_KAFKA = 0, 1, 2
+
+
+class ReplyOut(C.Structure):
+    """l7g_reply_out_t."""
+    _fields_ = [("buf", C.c_void_p), ("cap", C.c_uint64), ("off", C.c_void_p), ("len", C.c_void_p),
+                ("total", C.c_void_p)]
+
 
 _libs = {}
 
@@ -165,6 +173,12 @@ def load(path=None):
                                                  C.POINTER(LogOut)]
         lib.l7g_kafka_api_key_name.restype = cp
         lib.l7g_kafka_api_key_name.argtypes = [C.c_int16]
+    # (the same for the deny replies: tests/test_deny_replies_host.py)
+    if hasattr(lib, "l7g_deny_replies"):
+        lib.l7g_deny_replies.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, C.POINTER(ReplyOut), vp]
+        lib.l7g_deny_replies_host.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, C.POINTER(ReplyOut)]
+        lib.l7g_deny_reply_template.restype = vp
+        lib.l7g_deny_reply_template.argtypes = [C.c_int, C.POINTER(C.c_size_t)]
     _libs[path] = lib
     return lib
 
@@ -190,6 +204,15 @@ def kafka_api_key_name(key):
     for a key it does not name (print that one in decimal)."""
     r = load().l7g_kafka_api_key_name(int(key))
     return r.decode() if r is not None else None
+
+
+def deny_reply_template(proto):
+    """The fixed reply a denied request on a PROTO_HTTP, PROTO_CASSANDRA or
+    PROTO_R2D2 connection is answered with (csrc/deny_templates.h; cassandra's
+    before its three request bytes are set); b"" for any other protocol."""
+    n = C.c_size_t(0)
+    p = load().l7g_deny_reply_template(int(proto), C.byref(n))
+    return C.string_at(p, n.value) if p else b""
 
 
 def kafka_deny_response(req):

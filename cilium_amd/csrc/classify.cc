@@ -2,6 +2,7 @@
 // runs, on which lists, with which per-stream scratch, in which order.
 #include <algorithm>
 
+#include "deny_templates.h"
 #include "engine_state.h"
 
 // (0 in a variant build: the leg without the second Kafka grid, for A/B)
@@ -350,7 +351,49 @@ int CassReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const u
     return (int)rc;
 }
 
+// l7g_deny_replies: the post-pass over a classified batch, on the caller's
+// stream with that stream's reply scratch.  Nothing of l7g_classify's plan is
+// involved: the kernels read the verdicts and the connection table.
+int DenyReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                const uint32_t *conn, uint32_t n, const uint8_t *verdict, const l7g_reply_out_t *out, void *stream) {
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->device < 0) return (int)hipErrorNoDevice;
+    if (!out || !out->off || !out->len || !out->total || (!out->buf && out->cap)) return (int)hipErrorInvalidValue;
+    if (n && (!off || !len || !conn || !verdict)) return (int)hipErrorInvalidValue;
+    hipError_t rc = hipSetDevice(e->device);
+    if (rc == hipSuccess) rc = Upload(e);  // (the connection table the kernels read)
+    if (rc != hipSuccess) return (int)rc;
+    hipStream_t s = (hipStream_t)stream;
+    StreamScratch *S = nullptr;
+    if ((rc = GetScratch(e, s, &S)) != hipSuccess) return (int)rc;
+    const size_t need = DenyRepliesScratchBytes(n);
+    if (need == 0) return (int)hipErrorInvalidValue;
+    if ((rc = S->Grow(&S->d_reply, &S->reply_cap, need, need)) != hipSuccess) return (int)rc;
+    const Batch B{arena, arena_len, off, len, conn, e->d_conns, const_cast<uint8_t *>(verdict), nullptr, nullptr, n,
+                  (uint32_t)e->conns.size()};
+    rc = LaunchDenyReplies(B, out->buf, out->cap, out->off, out->len, out->total, S->d_reply, S->reply_cap, s);
+    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
+    if (rc == hipSuccess) S->launched = true;
+    return (int)rc;
+}
+
 extern "C" {
+
+int l7g_deny_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                     const uint32_t *conn, uint32_t n, const uint8_t *verdict, const l7g_reply_out_t *out,
+                     void *stream) {
+    return DenyReplies(e, arena, arena_len, off, len, conn, n, verdict, out, stream);
+}
+
+const uint8_t *l7g_deny_reply_template(int proto, size_t *len) {
+    const uint8_t *p = nullptr;
+    size_t n = 0;
+    if (proto == L7G_PROTO_HTTP) { p = reinterpret_cast<const uint8_t *>(kDenied403); n = kDenied403Len; }
+    if (proto == L7G_PROTO_CASSANDRA) { p = kCassUnauth; n = kCassUnauthLen; }
+    if (proto == L7G_PROTO_R2D2) { p = reinterpret_cast<const uint8_t *>(kR2Error); n = kR2ErrorLen; }
+    if (len) *len = n;
+    return p;
+}
 
 int l7g_cass_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
                      const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream) {

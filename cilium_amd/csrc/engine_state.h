@@ -54,6 +54,9 @@ struct StreamScratch {
     // large NFAs' state sets: a lane's 2 W words for each lane of a launch (grow-only)
     uint64_t *d_bignfa = nullptr;
     size_t bignfa_bytes = 0;
+    // l7g_deny_replies: [counters | Kafka index list | scan temporary storage] (bytes, grow-only)
+    void *d_reply = nullptr;
+    size_t reply_cap = 0;
     // completion of the last call's kernels on this stream
     hipEvent_t done_ev = nullptr;
     bool launched = false;
@@ -83,7 +86,8 @@ struct StreamScratch {
         if (fork_ev) hipEventDestroy(fork_ev);
         if (join_ev) hipEventDestroy(join_ev);
         if (side) hipStreamDestroy(side);
-        for (void *p : {(void *)d_bignfa, (void *)d_grp, (void *)d_sel, (void *)d_nfa, (void *)d_hist, d_use, (void *)d_work})
+        for (void *p : {(void *)d_bignfa, (void *)d_grp, (void *)d_sel, (void *)d_nfa, (void *)d_hist, d_use, (void *)d_work,
+                        d_reply})
             if (p) hipFree(p);
         if (done_ev) hipEventDestroy(done_ev);
     }
@@ -126,10 +130,15 @@ struct HostCtx {
     // l7g_classify_logged_host: [records | topic rows], on the device and pinned (grow-only)
     uint8_t *log_dev = nullptr, *log_pin = nullptr;
     size_t log_cap = 0;
+    // l7g_deny_replies_host: [verdict in | off | len | total | reply bytes], on the device and pinned (grow-only)
+    uint8_t *reply_dev = nullptr, *reply_pin = nullptr;
+    size_t reply_cap = 0;
     ~HostCtx() {
         if (s) hipStreamSynchronize(s);
         if (log_dev) hipFree(log_dev);
         if (log_pin) hipHostFree(log_pin);
+        if (reply_dev) hipFree(reply_dev);
+        if (reply_pin) hipHostFree(reply_pin);
         if (dev) hipFree(dev);
         if (pin_in) hipHostFree(pin_in);
         if (pin_out) hipHostFree(pin_out);
@@ -305,6 +314,9 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
              const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed, uint64_t *counters,
              void *stream, const uint32_t *host_conn, const CopyIn *pre = nullptr, bool *signaled = nullptr,
              const LogOut *log = nullptr);
+// classify.cc: l7g_deny_replies (device pointers; takes e->mu)
+int DenyReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                const uint32_t *conn, uint32_t n, const uint8_t *verdict, const l7g_reply_out_t *out, void *stream);
 void StopServices(l7g_engine *e);  // service.cc, as the next two
 void ReleaseServiceCUs(l7g_engine *e);
 bool ServiceTry(l7g_engine *e, uint32_t n, uint64_t arena_len, const HostIn &in, uint8_t *verdict, int32_t *rule,

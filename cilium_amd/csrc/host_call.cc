@@ -335,6 +335,88 @@ int l7g_classify_logged_host(l7g_engine *e, const uint8_t *arena, uint64_t arena
     return (int)rc;
 }
 
+// l7g_deny_replies with host buffers, over the calling thread's stream and
+// staging: the inputs and the verdicts copied in, the reply kernels, the
+// sizes copied out and waited for, then the bytes that were written.  The
+// replies that fit under cap are a prefix of the batch (off[] is a prefix
+// sum), so what the device wrote is one piece, buf[0, W) with W the last
+// fitting reply's end: only that is copied to the caller's buffer.  The reply
+// staging is [verdict | off | len | total | cap reply bytes], on the device and
+// pinned, grow-only per calling thread.
+int l7g_deny_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                          const uint32_t *len, const uint32_t *conn, uint32_t n, const uint8_t *verdict,
+                          const l7g_reply_out_t *out) {
+    if (e->device < 0) return (int)hipErrorNoDevice;
+    if (!out || !out->off || !out->len || !out->total || (!out->buf && out->cap)) return (int)hipErrorInvalidValue;
+    if (n && (!off || !len || !conn || !verdict)) return (int)hipErrorInvalidValue;
+    uint8_t *pa;
+    uint64_t *po;
+    uint32_t *pl, *pc;
+    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
+    if (rc0 != 0) return rc0;
+    if (n) {
+        memcpy(po, off, (size_t)n * 8);
+        memcpy(pl, len, (size_t)n * 4);
+        memcpy(pc, conn, (size_t)n * 4);
+    }
+    if (arena_len) memcpy(pa, arena, arena_len);
+    HostCtx *H = nullptr;
+    hipError_t rc = HostEnter(e, &H);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t o_off = ((size_t)n + 15) & ~(size_t)15, o_len = o_off + (size_t)n * 8;
+    const size_t o_tot = (o_len + (size_t)n * 4 + 15) & ~(size_t)15, o_buf = o_tot + 16;
+    const size_t need = o_buf + out->cap;
+    if (need > H->reply_cap) {
+        hipStreamSynchronize(H->s);
+        if (H->reply_dev) hipFree(H->reply_dev);
+        if (H->reply_pin) hipHostFree(H->reply_pin);
+        H->reply_dev = H->reply_pin = nullptr;
+        H->reply_cap = 0;
+        const size_t cap = need + need / 4;
+        if ((rc = hipMalloc(&H->reply_dev, cap)) != hipSuccess) return (int)rc;
+        if ((rc = hipHostMalloc(&H->reply_pin, cap, hipHostMallocDefault)) != hipSuccess) return (int)rc;
+        H->reply_cap = cap;
+    }
+    const size_t nn = CallNn(n);
+    uint8_t *d_in = H->dev, *d_r = H->reply_dev, *p_r = H->reply_pin;
+    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
+    if (rc == hipSuccess && n) {
+        memcpy(p_r, verdict, n);
+        rc = hipMemcpyAsync(d_r, p_r, n, hipMemcpyHostToDevice, H->s);
+    }
+    const l7g_reply_out_t dout{out->cap ? d_r + o_buf : nullptr, out->cap, (uint64_t *)(d_r + o_off),
+                               (uint32_t *)(d_r + o_len), (uint64_t *)(d_r + o_tot)};
+    if (rc == hipSuccess)
+        rc = (hipError_t)DenyReplies(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
+                                     (const uint32_t *)(d_in + CallLenOff(nn)), (const uint32_t *)(d_in + CallConnOff(nn)),
+                                     n, d_r, &dout, H->s);
+    if (rc == hipSuccess)
+        rc = hipMemcpyAsync(p_r + o_off, d_r + o_off, o_buf - o_off, hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
+    if (rc != hipSuccess) return (int)rc;
+    const uint64_t *h_off = (const uint64_t *)(p_r + o_off);
+    const uint32_t *h_len = (const uint32_t *)(p_r + o_len);
+    // the last reply that fits: off + len never decreases
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t m = lo + (hi - lo) / 2;
+        if (h_off[m] + h_len[m] <= out->cap) lo = m + 1; else hi = m;
+    }
+    const uint64_t W = lo ? h_off[lo - 1] + h_len[lo - 1] : 0;
+    if (W) {
+        rc = hipMemcpyAsync(p_r + o_buf, d_r + o_buf, W, hipMemcpyDeviceToHost, H->s);
+        if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
+        if (rc != hipSuccess) return (int)rc;
+        memcpy(out->buf, p_r + o_buf, W);
+    }
+    if (n) {
+        memcpy(out->off, h_off, (size_t)n * 8);
+        memcpy(out->len, h_len, (size_t)n * 4);
+    }
+    memcpy(out->total, p_r + o_tot, 16);
+    return 0;
+}
+
 // l7g_cass_replies with host buffers, over the calling thread's stream and
 // staging: one copy in, the reply kernels, one copy out, a wait.
 int l7g_cass_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,

@@ -19,6 +19,11 @@ hipError_t LaunchKafkaClassify(const Batch &B, const KafkaTables &T, const uint3
                                const LogOut *log = nullptr);
 // the logged calls' post-pass (kernels/http_log.hip): the records of every request but Kafka's
 hipError_t LaunchHttpLog(const Batch &B, LogRec *rec, hipStream_t stream);
+// l7g_deny_replies (kernels/deny_reply.hip): the replies of the requests whose verdict is DENY, packed
+// in request order (B.verdict is read; B.rule and B.consumed are not used)
+size_t DenyRepliesScratchBytes(uint32_t n);
+hipError_t LaunchDenyReplies(const Batch &B, uint8_t *buf, uint64_t cap, uint64_t *roff, uint32_t *rlen,
+                             uint64_t *total, void *scratch, size_t scratch_bytes, hipStream_t stream);
 hipError_t LaunchKafkaInflate(const Batch &B, const uint32_t *zlist, const uint32_t *zcount, uint8_t *region,
                               hipStream_t stream);
 uint32_t KafkaInflateBlocks();

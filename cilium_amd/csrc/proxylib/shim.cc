@@ -57,6 +57,7 @@
 #include "../../../include/l7gpu.h"
 #include "../../../include/proxylib_abi.h"
 #include "../capi_internal.h"
+#include "../deny_templates.h"
 #include "../kernels/cass_parse.h"
 #include "../regex/unicode_tables.h"
 
@@ -181,10 +182,10 @@ long FindCRLF(const std::string &d, size_t from = 0) {
 }
 
 const char kDeniedText[] = "CLIENT_ERROR access denied\r\n";  // text/parser.go:327
-// Envoy's local reply for a denied HTTP request: sendLocalReply(Forbidden,
-// denied_403_body = "Access denied" + CRLF) (envoy/cilium_l7policy.cc:90-96,171-177)
-const char kDenied403[] =
-    "HTTP/1.1 403 Forbidden\r\ncontent-length: 15\r\ncontent-type: text/plain\r\n\r\nAccess denied\r\n";
+// (the HTTP 403, the cassandra unauthorized frame and r2d2's error line: deny_templates.h)
+using l7::kCassUnauth;
+using l7::kDenied403;
+using l7::kR2Error;
 const uint8_t kDeniedBinary[37] = {0x81, 0, 0, 0, 0, 0, 0, 8, 0, 0, 0, 0x0d, 0, 0, 0, 0, 0, 0, 0,
                                    0,    0, 0, 0, 0, 'a', 'c', 'c', 'e', 's', 's', ' ', 'd', 'e', 'n', 'i', 'e', 'd'};
 
@@ -293,9 +294,6 @@ std::string CassEmptyUse() {
     return f + q;
 }
 
-const uint8_t kCassUnauth[35] = {0, 0, 0, 0, 0, 0, 0, 0, 0x1a, 0, 0, 0x21, 0, 0, 0x14, 'R', 'e', 'q',
-                                 'u', 'e', 's', 't', ' ', 'U', 'n', 'a', 'u', 't', 'h', 'o', 'r', 'i', 'z',
-                                 'e', 'd'};  // unauthMsgBase (cassandraparser.go:269-278)
 const uint8_t kCassUnprepared[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0x1a, 0, 0, 0x25, 0};  // unpreparedMsgBase (:284-292)
 
 struct Cached {
@@ -908,7 +906,7 @@ struct Connection {
             return FILTEROP_PASS;
         }
         Log(kEntryDenied, l7);
-        Inject(true, "ERROR\r\n", 7);
+        Inject(true, kR2Error, l7::kR2ErrorLen);
         return FILTEROP_DROP;
     }
 

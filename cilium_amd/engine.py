@@ -187,6 +187,56 @@ class Engine:
             raise RuntimeError(f"l7g_classify_logged_host failed: HIP error {rc}")
         return v, r, c, rec, topics
 
+    # ---------------------------------------------------------- deny replies
+    def deny_replies_device(self, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, verdict_ptr, buf_ptr, cap,
+                            reply_off_ptr, reply_len_ptr, total_ptr, stream=0):
+        """l7g_deny_replies: the replies of the requests whose verdict is DENY,
+        packed in request order into buf_ptr[0, cap) (0 with cap 0: sizes
+        only); reply_off_ptr (n uint64), reply_len_ptr (n uint32) and total_ptr
+        (2 uint64) are always written.  All pointers are device addresses."""
+        ro = _lib.ReplyOut(buf_ptr or None, cap, reply_off_ptr, reply_len_ptr, total_ptr)
+        rc = self._lib.l7g_deny_replies(self._h, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, verdict_ptr,
+                                        C.byref(ro), stream or None)
+        if rc != 0:
+            raise RuntimeError(f"l7g_deny_replies failed: HIP error {rc}")
+
+    def deny_replies_arrays(self, arena, offsets, lengths, conn_ids, verdict, cap=0, buf=None):
+        """l7g_deny_replies_host on host buffers: returns (buf, off, len,
+        total); buf is a uint8 array of cap bytes (the caller's, when given:
+        only the replies that fit are written into it)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        v = np.ascontiguousarray(verdict, dtype=np.uint8)
+        n = len(off)
+        if buf is None:
+            buf = np.zeros(cap, np.uint8)
+        ro_off = np.zeros(n, np.uint64)
+        ro_len = np.zeros(n, np.uint32)
+        total = np.zeros(2, np.uint64)
+        ro = _lib.ReplyOut(buf.ctypes.data if cap else None, cap, ro_off.ctypes.data, ro_len.ctypes.data,
+                           total.ctypes.data)
+        rc = self._lib.l7g_deny_replies_host(self._h, arena.ctypes.data, arena.nbytes, off.ctypes.data, ln.ctypes.data,
+                                             cid.ctypes.data, n, v.ctypes.data, C.byref(ro))
+        if rc != 0:
+            raise RuntimeError(f"l7g_deny_replies_host failed: HIP error {rc}")
+        return buf, ro_off, ro_len, total
+
+    def deny_replies(self, arena, offsets, lengths, conn_ids, verdict, cap=None):
+        """What to send back for each denied request (host buffers): a list of
+        bytes per request, b"" where there is nothing to send (the verdict is
+        not DENY, a memcached connection, a Kafka request without a response).
+        cap=None sizes first, then writes; with a cap, a reply that does not
+        fit under it comes back as None."""
+        if cap is None:
+            _, _, _, total = self.deny_replies_arrays(arena, offsets, lengths, conn_ids, verdict)
+            cap = int(total[0])
+        buf, ro_off, ro_len, _ = self.deny_replies_arrays(arena, offsets, lengths, conn_ids, verdict, cap)
+        raw = buf.tobytes()
+        return [b"" if l == 0 else (raw[o:o + l] if o + l <= cap else None)
+                for o, l in zip(ro_off.tolist(), ro_len.tolist())]
+
     # ---------------------------------------------------- cassandra sessions
     def cass_sessions(self, max_statements):
         """Device-resident cassandra sessions (l7g_cass_sessions_enable): with

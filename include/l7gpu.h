@@ -28,6 +28,12 @@
  *                                                                  vendor/github.com/optiopay/kafka/proto/messages.go:124-165,
  *                       memcached text line / binary header        proxylib/memcached/text/parser.go:72-262,
  *                                                                  proxylib/memcached/binary/parser.go:72-139
+ *   l7g_deny_replies    what is sent back for a DENY: req.CreateResponse(ErrTopicAuthorizationFailed)
+ *                                                                  pkg/proxy/kafka.go:249-261,
+ *                                                                  pkg/kafka/response.go:81-315,
+ *                       Envoy's 403 local reply                    envoy/cilium_l7policy.cc:90-96,171-177,
+ *                       the cassandra / r2d2 parsers' injected errors
+ *                                                                  proxylib/cassandra/cassandraparser.go:269-278
  *   counters argument   Endpoint.UpdateProxyStatistics counters    pkg/endpoint/endpoint.go:2207-2233
  *   of l7g_classify     (per-rule allow hits + per-verdict totals, accumulated on the device)
  *
@@ -277,6 +283,75 @@ int l7g_classify_logged_host(l7g_engine *e, const uint8_t *arena, uint64_t arena
 /* The API key's name as the policy language spells it (apiKeyToString,
  * pkg/proxy/kafka.go:162-167); NULL = unknown: print the key in decimal. */
 const char *l7g_kafka_api_key_name(int16_t key);
+
+/* Deny replies (opt-in; l7g_classify and everything it launches are untouched
+ * by it).  A post-pass over a classified batch: for every request whose
+ * verdict is L7G_DENY, the bytes the reference's enforcement point sends back,
+ * packed in request order, with no host pass over the request bytes.
+ *
+ *   Kafka      req.CreateResponse(ErrTopicAuthorizationFailed), every topic and
+ *              partition of the request echoed with errno 29
+ *              (pkg/proxy/kafka.go:249-261, pkg/kafka/request.go:158-182,
+ *              pkg/kafka/response.go:81-315, the encoders of
+ *              vendor/.../proto/messages.go:610,911,1117,1342,1531,1716,1975):
+ *              byte for byte what l7g_kafka_deny_response(request) writes, and
+ *              nothing (len 0) where it returns -1 -- an untyped API key, or
+ *              bytes that fail the typed decode
+ *   HTTP       Envoy's 403 local reply, 87 bytes: sendLocalReply(Forbidden,
+ *              "Access denied\r\n") (envoy/cilium_l7policy.cc:90-96,171-177)
+ *   cassandra  the 35-byte unauthorized frame, unauthMsgBase
+ *              (proxylib/cassandra/cassandraparser.go:269-278), with byte 0 =
+ *              0x80 | (request byte 0 & 7) and bytes 2-3 = the request's stream
+ *              id; nothing for a request shorter than 4 bytes
+ *   r2d2       "ERROR\r\n" (proxylib/r2d2/r2d2parser.go:140-214)
+ *   memcached  nothing (len 0), on purpose.  Whether and when a denied
+ *              memcached request is answered depends on the connection's reply
+ *              queue: the text parser injects at once only when the queue is
+ *              empty and honours noreply, the binary parser goes by
+ *              request / reply counters and enqueues twice.  The batch calls
+ *              keep no such state; the proxylib shim does, per connection.
+ * The protocol is the connection's (L7G_CONN_PROXYLIB connections included),
+ * not the bytes': a DENY on an HTTP connection gives the 403 whatever the
+ * request holds.
+ *
+ * verdict is what a classify call on the same stream wrote, or anything the
+ * caller supplies: the call is memory-safe for any verdict array.  len[i] is 0
+ * for every request whose verdict is not L7G_DENY, whose connection index is
+ * outside the table or whose bytes are outside the arena.
+ *
+ * off, len and total are written for all n requests whatever cap is: reply i
+ * is buf[off[i], off[i] + len[i]), off[] is the exclusive prefix sum of len[]
+ * (a connection's consecutive requests have their replies contiguous and in
+ * order), total[0] the bytes all replies need and total[1] the replies with
+ * len > 0.  Reply i is written if and only if off[i] + len[i] <= cap, and no
+ * byte at or past cap is touched: a caller that sees total[0] > cap calls again
+ * with a larger buffer (buf NULL with cap 0 asks for the sizes only).
+ *
+ * All pointers are device memory for l7g_deny_replies, which is asynchronous on
+ * `stream` and uses an engine-owned scratch, per stream and grow-only like
+ * l7g_classify's: 256 + 4 n bytes (rounded up to 256) plus the prefix sum's
+ * temporary storage (hipcub::DeviceScan: 9 KiB at n = 2^20, 1 MiB at 2^27).
+ * n is at most 2^31 - 1.  l7g_deny_replies_host takes host memory (copies in, runs,
+ * copies out, synchronises; the calling thread's stream, and a staging of 16 n
+ * + cap bytes on the device and pinned, grow-only per calling thread).
+ * Returns 0 or a hipError_t: hipErrorNoDevice on a host-only engine,
+ * hipErrorInvalidValue for a NULL off, len or total or buf NULL with cap > 0.
+ *
+ * l7g_deny_reply_template: the fixed reply of L7G_PROTO_HTTP, _CASSANDRA
+ * (before its three request bytes are set) or _R2D2 and its length; NULL and 0
+ * for a protocol without one. */
+typedef struct {
+    uint8_t  *buf;   uint64_t cap;   /* reply bytes; buf may be NULL with cap 0 (sizes only) */
+    uint64_t *off;   uint32_t *len;  /* n each: reply i is buf[off[i], off[i]+len[i]); len 0 = nothing to send */
+    uint64_t *total;                 /* 2 words: [0] bytes all replies need, [1] replies with len > 0 */
+} l7g_reply_out_t;
+int l7g_deny_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                     const uint32_t *conn, uint32_t n, const uint8_t *verdict, const l7g_reply_out_t *out,
+                     void *stream);
+int l7g_deny_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                          const uint32_t *len, const uint32_t *conn, uint32_t n, const uint8_t *verdict,
+                          const l7g_reply_out_t *out);
+const uint8_t *l7g_deny_reply_template(int proto, size_t *len);
 
 /* Cassandra sessions (off by default; with them off every answer is the
  * stateless one, byte for byte).
