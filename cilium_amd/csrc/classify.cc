@@ -86,7 +86,8 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
     // The kernels each classify only their own protocol's requests, so a
     // mixed batch needs one launch per protocol present.  When the engine
     // serves more than one protocol, partition_kernel runs first: it writes
-    // the Kafka and memcached index lists those two kernels walk, and answers
+    // the lists the classifiers walk (Kafka indices; memcached and HTTP packed
+    // entries, ListEnt in device_tables.h), and answers
     // the requests no classifier owns (unknown connection, no parser) itself.
     // A single-protocol HTTP or memcached engine skips it; its one kernel walks the whole batch
     // and answers those requests.
@@ -117,16 +118,19 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
     if (n >= kPartitionMin) ReleaseServiceCUs(e);  // (persistent grids: every CU)
     StreamScratch *S = nullptr;
     if ((rc = GetScratch(e, s, &S)) != hipSuccess) return (int)rc;
-    uint32_t *sel_k = nullptr, *sel_m = nullptr, *sel_h = nullptr, *sel_z = nullptr, *cnt = nullptr;
+    uint32_t *sel_k = nullptr, *sel_z = nullptr, *cnt = nullptr;
+    ListEnt *sel_m = nullptr, *sel_h = nullptr;
     if (partitioned) {
         const size_t need = kCntWords + PartitionListWords(n);
         rc = S->Grow(&S->d_sel, &S->sel_cap, need, need * sizeof(uint32_t));
         if (rc != hipSuccess) return (int)rc;
         cnt = S->d_sel;  // (its words: device_tables.h kCnt*)
-        sel_k = S->d_sel + kCntWords;
-        sel_m = sel_k + L7_KAFKA_CLASSES * (size_t)n;
+        // the entry lists first: 16-byte aligned behind the counts block
+        static_assert(kCntWords % 4 == 0 && sizeof(ListEnt) == 16, "entry lists start on 16 bytes");
+        sel_m = reinterpret_cast<ListEnt *>(S->d_sel + kCntWords);
         sel_h = sel_m + (size_t)n;
-        sel_z = sel_h + (size_t)n;
+        sel_k = reinterpret_cast<uint32_t *>(sel_h + (size_t)n);
+        sel_z = sel_k + L7_KAFKA_CLASSES * (size_t)n;
         if (rc == hipSuccess) rc = hipMemsetAsync(cnt, 0, kCntWords * sizeof(uint32_t), s);
         if (rc == hipSuccess && e->has_kafka && !e->d_zreg) {
             rc = hipEventCreateWithFlags(&e->zreg_ev, hipEventDisableTiming);
@@ -214,10 +218,12 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
                          ht.nrulesets <= kMaxGroupRulesets;
     if (rc == hipSuccess && grouped) {
         const size_t R = ht.nrulesets, segw = 3 * ((size_t)n / kGroupSegEntries + R + 1);
-        const size_t need = 8 + 2 * R + segw + 2 * (size_t)n;
+        const size_t need = 8 + 2 * R + segw + 5 * (size_t)n;
         rc = S->Grow(&S->d_grp, &S->grp_cap, need, need * sizeof(uint32_t));
-        uint32_t *ctl = S->d_grp, *hist = ctl + 8, *cursor = hist + R, *segs = cursor + R, *gsel = segs + segw,
-                 *gbig = gsel + n;
+        // (the big-image list holds entries, the general kernel's input: first, 16-byte aligned)
+        ListEnt *gbig = reinterpret_cast<ListEnt *>(S->d_grp);
+        uint32_t *ctl = S->d_grp + 4 * (size_t)n, *hist = ctl + 8, *cursor = hist + R, *segs = cursor + R,
+                 *gsel = segs + segw;
         if (rc == hipSuccess) rc = hipMemsetAsync(ctl, 0, (8 + R) * sizeof(uint32_t), s);
         if (rc == hipSuccess)
             rc = LaunchHttpGroup(B, ht, sel_h, cnt ? cnt + kCntHttp : nullptr, n, !partitioned, ctl, hist, cursor, segs,

@@ -37,8 +37,22 @@ constexpr int kCntKafkaWork = 26;                  // the Kafka kernel's entry c
 constexpr int kCntMcWork = 27;                     // the memcached kernel's chunk counter (persistent grid)
 constexpr int kCntHttpTiles = 28;                 // and the next word: HTTP tile counters (hot, general launch)
 constexpr int kCntKafkaZ = 31;                     // Kafka requests with compressed messages
-// the index lists behind the block, in words: L7_KAFKA_CLASSES x n Kafka, n memcached, n HTTP, n compressed Kafka
-constexpr size_t PartitionListWords(size_t n) { return (L7_KAFKA_CLASSES + 3) * n; }
+// One entry of the HTTP list and of the memcached lists (16 B, read as one uint4): what the partition
+// has loaded about the request anyway, so its classifier starts from one coalesced load instead of
+// the chain list -> conn_ids / offs / lens -> conns.
+//   x = request index, y = length, z = offset bits 0..31,
+//   w = rule set << 12 | connection flags (2 bits) << 10 | offset bits 32..41
+// w = kEntByIndex: only x holds; the reader takes everything from the index, as it does without a
+// list.  The partition writes that when the rule set is negative or >= 2^20 - 1, the offset >= 2^42, or
+// the request leaves the arena, so a packed entry always lies inside the arena; the reader still
+// checks rule set < nrulesets against its own tables.
+struct alignas(16) ListEnt { uint32_t x, y, z, w; };
+constexpr uint32_t kEntByIndex = 0xFFFFFFFFu;
+constexpr uint32_t kEntMaxRuleset = (1u << 20) - 1;  // (2^20 - 1 with every other bit set would read as kEntByIndex)
+L7_HD inline uint64_t l7_ent_off(uint32_t z, uint32_t w) { return (uint64_t)(w & 0x3FFu) << 32 | z; }
+// the lists behind the block, in words: n entries memcached, n entries HTTP (ListEnt, 4 words each),
+// then the index lists: L7_KAFKA_CLASSES x n Kafka, n compressed Kafka
+constexpr size_t PartitionListWords(size_t n) { return (8 + L7_KAFKA_CLASSES + 1) * n; }
 
 // Header slots recorded by the HTTP framer.
 enum : int { SLOT_METHOD = 0, SLOT_PATH = 1, SLOT_AUTHORITY = 2, SLOT_CUSTOM0 = 3 };
@@ -90,6 +104,16 @@ struct LogOut {
 // every kernel answers it UNSUPPORTED instead of reading past the arena.
 L7_HD inline bool l7_in_arena(uint64_t off, uint32_t len, uint64_t arena_len) {
     return off <= arena_len && (uint64_t)len <= arena_len - off;
+}
+// Word w of a request's list entry (ListEnt above), in two steps: the connection's part (bits 10..31;
+// a rule set that does not pack reads kEntMaxRuleset), then the request's.
+L7_HD inline uint32_t l7_ent_head(int32_t ruleset, uint32_t flags) {
+    const uint32_t rs = ruleset < 0 || (uint32_t)ruleset >= kEntMaxRuleset ? kEntMaxRuleset : (uint32_t)ruleset;
+    return rs << 12 | (flags & 3u) << 10;
+}
+L7_HD inline uint32_t l7_ent_word(uint32_t head, uint64_t off, uint32_t len, uint64_t arena_len) {
+    if ((head >> 12) >= kEntMaxRuleset || off >> 42 || !l7_in_arena(off, len, arena_len)) return kEntByIndex;
+    return (head & ~0x3FFu) | (uint32_t)(off >> 32);
 }
 
 // ---------------- HTTP ----------------

@@ -33,8 +33,8 @@ using namespace l7;
 // different streams use different scratch and run concurrently; calls on one
 // stream are ordered by the stream itself.
 struct StreamScratch {
-    // protocol split (grow-only): [counts(kCntWords) | L7_KAFKA_CLASSES x n Kafka idx | n memcached idx |
-    // n HTTP idx | n idx of Kafka requests with compressed messages]
+    // protocol split (grow-only), in words: [counts(kCntWords) | n memcached entries (ListEnt, 4 words each) |
+    // n HTTP entries | L7_KAFKA_CLASSES x n Kafka idx | n idx of Kafka requests with compressed messages]
     uint32_t *d_sel = nullptr;
     size_t sel_cap = 0;
     // NFA pre-pass results, u64 per request (grow-only)
@@ -48,7 +48,8 @@ struct StreamScratch {
     // work counters of unpartitioned batches (HTTP tile counters), allocated on first use
     uint32_t *d_work = nullptr;
     // HTTP requests grouped by rule set (kernels/http_group.hip), grow-only:
-    // [ctl(8) | hist(R) | cursor(R) | segments(3 x (n / kGroupSegEntries + R + 1)) | grouped list(n) | big-image list(n)]
+    // [big-image list(n entries, 4 words each) | ctl(8) | hist(R) | cursor(R) |
+    //  segments(3 x (n / kGroupSegEntries + R + 1)) | grouped list(n)]
     uint32_t *d_grp = nullptr;
     size_t grp_cap = 0;
     // large NFAs' state sets: a lane's 2 W words for each lane of a launch (grow-only)

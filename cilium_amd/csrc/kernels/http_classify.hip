@@ -1889,11 +1889,15 @@ __device__ __forceinline__ bool lat_fast(const Lane &L, const uint8_t *img, uint
 // no parser) UNSUPPORTED; false when partition_kernel has answered them.
 // sel: the HTTP requests of a mixed batch (partition_kernel), tiles of 64
 // list entries; null: the whole batch, tiles of 64 consecutive requests.
+// An entry (ListEnt, device_tables.h) carries the request's length, offset
+// and rule set, so a lane sets itself up from one coalesced 16-byte load;
+// conn_ids, offs, lens and conns are read only for kEntByIndex entries, which
+// take the steps of a request without a list.
 // kGrab: tiles taken from the counter per atomic (1, or 4 for short requests;
 // the launcher's note).  Separate instantiations keep kGrab == 1 the round-4
 // code (+1-2 % on cfg2 when the grab size was a runtime value).
 template <bool kHot, uint32_t kGrab = 1>
-__global__ __launch_bounds__(kBlock) void http_classify_kernel(Batch B, HttpTables T, const uint32_t *__restrict__ sel,
+__global__ __launch_bounds__(kBlock) void http_classify_kernel(Batch B, HttpTables T, const uint4 *__restrict__ sel,
                                                                const uint32_t *__restrict__ sel_count,
                                                                uint32_t answer_other, uint32_t *__restrict__ tile_ctr) {
     const uint8_t *__restrict__ arena = B.arena;
@@ -1944,7 +1948,9 @@ __global__ __launch_bounds__(kBlock) void http_classify_kernel(Batch B, HttpTabl
         next = tile + stride;
         Lane L;
         const uint32_t slot = tile * 64 + lane;
-        L.idx = sel ? (slot < m ? sel[slot] : n) : slot;
+        uint4 e = make_uint4(slot, 0, 0, kEntByIndex);
+        if (sel) e = slot < m ? sel[slot] : make_uint4(n, 0, 0, kEntByIndex);
+        L.idx = e.x;
         L.done = true;
         L.owed = false;
         L.verdict = V_UNSUPPORTED;
@@ -1955,8 +1961,12 @@ __global__ __launch_bounds__(kBlock) void http_classify_kernel(Batch B, HttpTabl
         L.a0 = L.pa = L.w = L.lena = 0;
         const uint8_t *img = kHot ? s_img : nullptr;
         if (L.idx < n) {
-            const uint32_t ci = B.conn_ids[L.idx];
-            const DevConn conn = ci < nconns ? B.conns[ci] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
+            // a packed entry is an HTTP request on rule set w >> 12 (the partition's reading of its connection)
+            DevConn conn{(int32_t)(e.w >> 12), PROTO_HTTP, 0, 0xFFFF};
+            if (e.w == kEntByIndex) {
+                const uint32_t ci = B.conn_ids[L.idx];
+                conn = ci < nconns ? B.conns[ci] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
+            }
             // entries of other protocols belong to their own kernels; the HTTP
             // kernel answers entries whose connection is unknown or has no parser
             const bool mine = !L7_PROTO_OWNED(conn.proto) || conn.proto == PROTO_HTTP;
@@ -1964,8 +1974,12 @@ __global__ __launch_bounds__(kBlock) void http_classify_kernel(Batch B, HttpTabl
             const bool is_hot = http && hot_ok && conn.ruleset == hot;
             if (mine && !http && answer_other && (kHot || !hot_ok)) L.owed = true;  // unsupported connection: answered as is
             if (http && is_hot == kHot) {
-                const uint64_t off = B.offs[L.idx];
-                const uint32_t len = B.lens[L.idx];
+                uint64_t off = l7_ent_off(e.z, e.w);
+                uint32_t len = e.y;
+                if (e.w == kEntByIndex) {
+                    off = B.offs[L.idx];
+                    len = B.lens[L.idx];
+                }
                 if (!l7_in_arena(off, len, B.arena_len)) {  // outside the arena: out of contract
                     L.owed = true;
                 } else {
@@ -2005,7 +2019,7 @@ __global__ __launch_bounds__(kBlock) void http_classify_kernel(Batch B, HttpTabl
 // the tile kernel's.  stage: copy the hot rule set's image into LDS (the
 // resident service stages it once for its lifetime).  Ends with a barrier.
 template <bool kHot>
-__device__ __forceinline__ void lat_body(const Batch &B, const HttpTables &T, const uint32_t *__restrict__ sel,
+__device__ __forceinline__ void lat_body(const Batch &B, const HttpTables &T, const uint4 *__restrict__ sel,
                                          const uint32_t *__restrict__ sel_count, uint32_t answer_other, uint8_t *lds,
                                          bool stage) {
     const uint8_t *__restrict__ arena = B.arena;
@@ -2042,7 +2056,7 @@ __device__ __forceinline__ void lat_body(const Batch &B, const HttpTables &T, co
     for (uint32_t r = blockIdx.x * kWaves + wave; r < m; r += gridDim.x * kWaves) {
         LAT_T0
         Lane L;
-        L.idx = sel ? sel[r] : r;
+        L.idx = sel ? sel[r].x : r;  // (a small call: the entry's index, the rest as without a list)
         L.done = true;
         L.owed = false;
         L.verdict = V_UNSUPPORTED;
@@ -2088,7 +2102,7 @@ __device__ __forceinline__ void lat_body(const Batch &B, const HttpTables &T, co
 
 template <bool kHot>
 // ci: the call's inputs to copy first (a one-workgroup launch), or none.
-__global__ __launch_bounds__(kBlock) void http_latency_kernel(Batch B, HttpTables T, const uint32_t *__restrict__ sel,
+__global__ __launch_bounds__(kBlock) void http_latency_kernel(Batch B, HttpTables T, const uint4 *__restrict__ sel,
                                                               const uint32_t *__restrict__ sel_count,
                                                               uint32_t answer_other, CopyIn ci) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kLdsBytes];
@@ -2215,10 +2229,11 @@ __global__ __launch_bounds__(kBlock) void http_grouped_kernel(Batch B, HttpTable
 // HTTP connection uses another rule set) the general one.
 // latency: a small call, one request per wave (http_latency_kernel)
 // (ci: latency only, with one workgroup: copied by the first kernel launched)
-hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const uint32_t *sel, const uint32_t *sel_count,
+hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const ListEnt *ents, const uint32_t *sel_count,
                               bool any_cold, bool answer_other, uint32_t *tile_ctr, bool latency, const CopyIn *ci,
                               hipStream_t stream) {
     if (B.n == 0) return hipSuccess;
+    const uint4 *sel = reinterpret_cast<const uint4 *>(ents);
     static int num_cus = 0;
     if (num_cus == 0) {
         int dev = 0;
@@ -2260,7 +2275,7 @@ hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const uint32_
     // tile, the counter's queue shrinks (cfg5 HTTP 16.94 -> 16.87 ms, profiles/r5/ab5e_work_grab.log).
     const uint32_t per_wave = ntiles / (blocks * kWaves);
     const uint32_t grab = B.arena_len / B.n < 512 ? 4u : per_wave >= 64 ? 2u : 1u;
-    using Kern = void (*)(Batch, HttpTables, const uint32_t *, const uint32_t *, uint32_t, uint32_t *);
+    using Kern = void (*)(Batch, HttpTables, const uint4 *, const uint32_t *, uint32_t, uint32_t *);
     const Kern kHot = grab == 4 ? http_classify_kernel<true, 4> : grab == 2 ? http_classify_kernel<true, 2>
                                                                          : http_classify_kernel<true, 1>;
     const Kern kGen = grab == 4 ? http_classify_kernel<false, 4> : grab == 2 ? http_classify_kernel<false, 2>
@@ -2277,7 +2292,7 @@ hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const uint32_
 // segments, then the general kernel over the entries on rule sets whose image
 // exceeds the LDS budget (gbig, ctl[2] of them; ctl[3] its tile counter).
 hipError_t LaunchHttpGrouped(const Batch &B, const HttpTables &T, const uint32_t *gsel, const uint32_t *segs,
-                             const uint32_t *gbig, uint32_t *ctl, bool any_big, hipStream_t stream) {
+                             const ListEnt *gbig, uint32_t *ctl, bool any_big, hipStream_t stream) {
     if (B.n == 0) return hipSuccess;
     static int num_cus = 0;
     if (num_cus == 0) {
@@ -2290,7 +2305,8 @@ hipError_t LaunchHttpGrouped(const Batch &B, const HttpTables &T, const uint32_t
     const uint32_t blocks = min((ntiles + kWaves - 1) / kWaves, (uint32_t)num_cus);
     hipLaunchKernelGGL(http_grouped_kernel, dim3(blocks), dim3(kBlock), 0, stream, B, T, gsel, segs, ctl);
     if (any_big)
-        hipLaunchKernelGGL(http_classify_kernel<false>, dim3(blocks), dim3(kBlock), 0, stream, B, T, gbig, ctl + 2, 0u,
+        hipLaunchKernelGGL(http_classify_kernel<false>, dim3(blocks), dim3(kBlock), 0, stream, B, T,
+                           reinterpret_cast<const uint4 *>(gbig), ctl + 2, 0u,
                            ctl + 3);
     return hipGetLastError();
 }

@@ -28,7 +28,7 @@ constexpr int kPer = 8;  // entries per thread
 }  // namespace
 
 // The entry -> (request index, HTTP rule set or -1) step shared by the passes:
-// entry i of `sel` (the partition's HTTP list) or request i.
+// entry i of `sel` (the partition's HTTP list, ListEnt: its index) or request i.
 __device__ __forceinline__ int32_t group_rs(const Batch &B, const HttpTables &T, uint32_t idx, bool &other) {
     const uint32_t ci = B.conn_ids[idx];
     const DevConn c = ci < B.nconns ? B.conns[ci] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
@@ -39,7 +39,7 @@ __device__ __forceinline__ int32_t group_rs(const Batch &B, const HttpTables &T,
 }
 
 // hist[r] += the entries on rule set r
-__global__ __launch_bounds__(kBlock) void http_group_count_kernel(Batch B, HttpTables T, const uint32_t *__restrict__ sel,
+__global__ __launch_bounds__(kBlock) void http_group_count_kernel(Batch B, HttpTables T, const uint4 *__restrict__ sel,
                                                                   const uint32_t *__restrict__ sel_count,
                                                                   uint32_t *__restrict__ hist) {
     __shared__ uint32_t h[kMaxGroupRulesets];
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kBlock) void http_group_count_kernel(Batch B, HttpT
         const uint32_t i = start + k * kBlock + threadIdx.x;
         if (i < m) {
             bool other;
-            const int32_t r = group_rs(B, T, sel ? sel[i] : i, other);
+            const int32_t r = group_rs(B, T, sel ? sel[i].x : i, other);
             if (r >= 0) atomicAdd(&h[r], 1u);
         }
     }
@@ -127,11 +127,11 @@ __global__ __launch_bounds__(1024) void http_group_scan_kernel(HttpTables T, con
 // answer_other, entries on unknown connections or connections without a parser
 // are answered here (UNSUPPORTED), as the HTTP kernel would have.
 __global__ __launch_bounds__(kBlock) void http_group_scatter_kernel(Batch B, HttpTables T,
-                                                                    const uint32_t *__restrict__ sel,
+                                                                    const uint4 *__restrict__ sel,
                                                                     const uint32_t *__restrict__ sel_count,
                                                                     uint32_t *__restrict__ cursor,
                                                                     uint32_t *__restrict__ gsel,
-                                                                    uint32_t *__restrict__ gbig, uint32_t answer_other) {
+                                                                    uint4 *__restrict__ gbig, uint32_t answer_other) {
     __shared__ uint32_t h[kMaxGroupRulesets];
     const uint32_t nrs = T.nrulesets, m = sel ? *sel_count : B.n;
     for (uint32_t r = threadIdx.x; r < nrs; r += kBlock) h[r] = 0;
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kBlock) void http_group_scatter_kernel(Batch B, Htt
         const uint32_t i = start + k * kBlock + threadIdx.x;
         rs[k] = -1;
         if (i < m) {
-            idx[k] = sel ? sel[i] : i;
+            idx[k] = sel ? sel[i].x : i;
             bool other;
             rs[k] = group_rs(B, T, idx[k], other);
             if (rs[k] >= 0) rank[k] = atomicAdd(&h[rs[k]], 1u);
@@ -163,7 +163,8 @@ __global__ __launch_bounds__(kBlock) void http_group_scatter_kernel(Batch B, Htt
     for (int k = 0; k < kPer; k++)
         if (rs[k] >= 0) {
             const uint32_t at = h[rs[k]] + rank[k];
-            if (at >> 31) gbig[at & 0x7FFFFFFFu] = idx[k];
+            // (the general kernel's list: an entry that sends it to the index)
+            if (at >> 31) gbig[at & 0x7FFFFFFFu] = make_uint4(idx[k], 0, 0, kEntByIndex);
             else gsel[at] = idx[k];
         }
 }
@@ -171,15 +172,16 @@ __global__ __launch_bounds__(kBlock) void http_group_scatter_kernel(Batch B, Htt
 // ctl and hist must be zero on entry ((4 + nrulesets) words); cursor, segs,
 // gsel and gbig are written here.  n: entries in the list (an upper bound when
 // sel_count is on the device).
-hipError_t LaunchHttpGroup(const Batch &B, const HttpTables &T, const uint32_t *sel, const uint32_t *sel_count,
+hipError_t LaunchHttpGroup(const Batch &B, const HttpTables &T, const ListEnt *sel, const uint32_t *sel_count,
                            uint32_t n, bool answer_other, uint32_t *ctl, uint32_t *hist, uint32_t *cursor,
-                           uint32_t *segs, uint32_t *gsel, uint32_t *gbig, hipStream_t stream) {
+                           uint32_t *segs, uint32_t *gsel, ListEnt *gbig, hipStream_t stream) {
+    const uint4 *esel = reinterpret_cast<const uint4 *>(sel);
     if (n == 0 || T.nrulesets == 0 || T.nrulesets > kMaxGroupRulesets) return hipErrorInvalidValue;
     const uint32_t blocks = (n + kBlock * kPer - 1) / (kBlock * kPer);
-    hipLaunchKernelGGL(http_group_count_kernel, dim3(blocks), dim3(kBlock), 0, stream, B, T, sel, sel_count, hist);
+    hipLaunchKernelGGL(http_group_count_kernel, dim3(blocks), dim3(kBlock), 0, stream, B, T, esel, sel_count, hist);
     hipLaunchKernelGGL(http_group_scan_kernel, dim3(1), dim3(1024), 0, stream, T, hist, cursor, segs, ctl);
-    hipLaunchKernelGGL(http_group_scatter_kernel, dim3(blocks), dim3(kBlock), 0, stream, B, T, sel, sel_count, cursor,
-                       gsel, gbig, answer_other ? 1u : 0u);
+    hipLaunchKernelGGL(http_group_scatter_kernel, dim3(blocks), dim3(kBlock), 0, stream, B, T, esel, sel_count, cursor,
+                       gsel, reinterpret_cast<uint4 *>(gbig), answer_other ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -10,7 +10,8 @@
 
 namespace l7 {
 
-hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const uint32_t *sel, const uint32_t *sel_count,
+// sel (here, LaunchHttpGroup, LaunchMemcacheClassify): entry lists (ListEnt, device_tables.h)
+hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const ListEnt *sel, const uint32_t *sel_count,
                               bool any_cold, bool answer_other, uint32_t *tile_ctr, bool latency, const CopyIn *ci,
                               hipStream_t stream);
 hipError_t LaunchKafkaClassify(const Batch &B, const KafkaTables &T, const uint32_t *sel, const uint32_t *sel_count,
@@ -28,7 +29,7 @@ hipError_t LaunchKafkaInflate(const Batch &B, const uint32_t *zlist, const uint3
                               hipStream_t stream);
 uint32_t KafkaInflateBlocks();
 uint32_t KafkaInflateRegionBytes();
-hipError_t LaunchMemcacheClassify(const Batch &B, const McTables &T, const uint32_t *sel, const uint32_t *sel2,
+hipError_t LaunchMemcacheClassify(const Batch &B, const McTables &T, const ListEnt *sel, const ListEnt *sel2,
                                   const uint32_t *sel_count, bool answer_other, uint32_t scratch_lanes,
                                   hipStream_t stream, const CopyIn *ci = nullptr, int beside_slots = 0,
                                   uint32_t *work = nullptr);
@@ -53,7 +54,7 @@ size_t CountersScratchBytes();
 hipError_t LaunchFlowStats(const Batch &B, uint32_t nkeys, uint64_t *acc, hipStream_t stream);
 uint32_t FlowStatsMaxKeys();
 hipError_t LaunchHttpNfa(const Batch &B, const HttpTables &T, uint32_t scratch_lanes, hipStream_t stream);
-hipError_t LaunchPartition(const Batch &B, uint32_t *sel_kafka, uint32_t *sel_mc, uint32_t *sel_http, uint32_t *counts,
+hipError_t LaunchPartition(const Batch &B, uint32_t *sel_kafka, ListEnt *ent_mc, ListEnt *ent_http, uint32_t *counts,
                            hipStream_t stream);
 hipError_t LaunchFrameStreams(const uint8_t *arena, uint64_t arena_len, const uint64_t *s_off, const uint32_t *s_len,
                               const uint32_t *s_conn, uint32_t n, const DevConn *conns, uint32_t nconns,
@@ -63,11 +64,11 @@ hipError_t HttpPhaseTimes(uint64_t *out, bool reset);
 hipError_t KafkaPhaseTimes(uint64_t *out, bool reset);
 hipError_t LaunchCopyIn(const CopyIn &c, hipStream_t stream);
 hipError_t FramePhaseTimes(uint64_t *out, bool reset);
-hipError_t LaunchHttpGroup(const Batch &B, const HttpTables &T, const uint32_t *sel, const uint32_t *sel_count,
+hipError_t LaunchHttpGroup(const Batch &B, const HttpTables &T, const ListEnt *sel, const uint32_t *sel_count,
                            uint32_t n, bool answer_other, uint32_t *ctl, uint32_t *hist, uint32_t *cursor,
-                           uint32_t *segs, uint32_t *gsel, uint32_t *gbig, hipStream_t stream);
+                           uint32_t *segs, uint32_t *gsel, ListEnt *gbig, hipStream_t stream);
 hipError_t LaunchHttpGrouped(const Batch &B, const HttpTables &T, const uint32_t *gsel, const uint32_t *segs,
-                             const uint32_t *gbig, uint32_t *ctl, bool any_big, hipStream_t stream);
+                             const ListEnt *gbig, uint32_t *ctl, bool any_big, hipStream_t stream);
 hipError_t LaunchHttpService(SvcBox *box, const SvcStatic &S, const HttpTables &T, uint32_t seen0, uint64_t idle,
                              hipStream_t stream);
 hipError_t LaunchMemcacheService(SvcBox *box, const SvcStatic &S, const McTables &T, uint32_t seen0, uint64_t idle,

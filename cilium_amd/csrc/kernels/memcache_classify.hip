@@ -510,59 +510,50 @@ __device__ __forceinline__ void mc_one(const Batch &B, const McTables &T, const 
     mc_body<kNfa, kLds, kCh>(B, T, images, idx, off, len, conn, answer_other);
 }
 
+// The entries (ListEnt, device_tables.h) of a lane's kMcSortPer requests when
+// no list holds them (a memcached-only engine below the partition's floor):
+// what partition_kernel would have written, the loads phase by phase
+// (connection ids, connections, offsets / lengths).  ix: ~0u = no request.
+__device__ __forceinline__ void mc_entries(const Batch &B, const uint32_t (&ix)[kMcSortPer], uint4 (&e)[kMcSortPer]) {
+    uint32_t ci[kMcSortPer];
+    DevConn c[kMcSortPer];
+#pragma unroll
+    for (int r = 0; r < kMcSortPer; r++) ci[r] = ix[r] != ~0u ? B.conn_ids[ix[r]] : ~0u;
+#pragma unroll
+    for (int r = 0; r < kMcSortPer; r++) c[r] = ci[r] < B.nconns ? B.conns[ci[r]] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
+#pragma unroll
+    for (int r = 0; r < kMcSortPer; r++) {
+        e[r] = make_uint4(ix[r], 0, 0, kEntByIndex);
+        if (c[r].proto == PROTO_MEMCACHE && c[r].ruleset >= 0) {
+            const uint64_t of = B.offs[ix[r]];
+            e[r].y = B.lens[ix[r]];
+            e[r].z = (uint32_t)of;
+            e[r].w = l7_ent_word(l7_ent_head(c[r].ruleset, c[r].flags), of, e[r].y, B.arena_len);
+        }
+    }
+}
+
 // The parser each of a lane's kMcSortPer entries takes (memcached/parser.go:
 // 186-202: the connection's, else the one its first byte picks), and text
 // retrievals (get / gets / gat / gats) apart from the other commands, whose
 // lines are longer and parse more tokens: 0 text retrieval, 1 other text, 2
-// binary, 3 everything else, 4 no entry.  The loads go out phase by phase
-// (connection ids, connections, offsets / lengths, first bytes) so the lane
-// waits four memory latencies, not four per entry.
-// Also returned, for the classifying lane (no second fetch): the entry's
-// offset, length and connection (rsf: rule set << 12 | flags << 10 | offset
-// bits 32..41; ~0u: kind 3, or a field that does not fit, and the
-// classifying lane reads them itself).
-__device__ __forceinline__ void mc_kinds(const Batch &B, const McTables &T, const uint32_t (&ix)[kMcSortPer],
-                                         uint32_t (&kd)[kMcSortPer], uint64_t (&of)[kMcSortPer],
-                                         uint32_t (&ln)[kMcSortPer], uint32_t (&rsf)[kMcSortPer]) {
-    uint32_t ci[kMcSortPer], fl[kMcSortPer];
-#pragma unroll
-    for (int r = 0; r < kMcSortPer; r++) ci[r] = ix[r] != ~0u ? B.conn_ids[ix[r]] : ~0u;
+// binary, 3 everything else (an entry by index, an empty request, a rule set
+// the tables do not have), 4 no entry.  One load phase: the first byte, and
+// only where the connection's flags leave the parser open.
+__device__ __forceinline__ void mc_kinds(const Batch &B, const McTables &T, const uint4 (&e)[kMcSortPer],
+                                         uint32_t (&kd)[kMcSortPer]) {
+    uint32_t b0[kMcSortPer];
 #pragma unroll
     for (int r = 0; r < kMcSortPer; r++) {
-        kd[r] = ix[r] == ~0u ? 4 : 3;
-        fl[r] = 0;
-        rsf[r] = ~0u;
-        if (ci[r] < B.nconns) {
-            const DevConn c = B.conns[ci[r]];
-            if (c.proto == PROTO_MEMCACHE && c.ruleset >= 0 && (uint32_t)c.ruleset < T.nrulesets) {
-                kd[r] = 0;
-                fl[r] = c.flags;
-                rsf[r] = c.ruleset < (1 << 20) ? (uint32_t)c.ruleset << 12 | (c.flags & 3u) << 10 : ~0u;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < kMcSortPer; r++) {
-        of[r] = 0;
-        ln[r] = 0;
-        if (kd[r] == 0) {
-            of[r] = B.offs[ix[r]];
-            ln[r] = B.lens[ix[r]];
-            if (ln[r] == 0 || !l7_in_arena(of[r], ln[r], B.arena_len)) {
-                kd[r] = 3;
-                rsf[r] = ~0u;
-            } else if (rsf[r] != ~0u) {
-                rsf[r] = of[r] >> 42 ? ~0u : rsf[r] | (uint32_t)(of[r] >> 32);  // (offsets past 4 TiB: fetched again)
-            }
-        }
+        kd[r] = e[r].x == ~0u ? 4 : e[r].w == kEntByIndex || e[r].y == 0 || (e[r].w >> 12) >= T.nrulesets ? 3 : 0;
+        b0[r] = kd[r] == 0 && ((e[r].w >> 10) & 3) != 2 ? B.arena[l7_ent_off(e[r].z, e[r].w)] : 0;  // (binary by its flags: not read)
     }
 #pragma unroll
     for (int r = 0; r < kMcSortPer; r++) {
         if (kd[r] != 0) continue;
-        const uint32_t b0 = B.arena[of[r]];
-        uint32_t mode = fl[r] & 3;
-        if (mode == 0) mode = b0 >= 0x80 ? 2 : 1;
-        kd[r] = mode == 2 ? 2 : b0 == 'g' ? 0 : 1;
+        uint32_t mode = (e[r].w >> 10) & 3;
+        if (mode == 0) mode = b0[r] >= 0x80 ? 2 : 1;
+        kd[r] = mode == 2 ? 2 : b0[r] == 'g' ? 0 : 1;
     }
 }
 
@@ -571,22 +562,23 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
-// sel: this protocol's request indices (partition_kernel, mixed batches), else
-// requests 0..n-1.  Each wave takes kMcWaveChunk list entries at a time,
-// reads each one's parser from its first byte (a line the classification
-// reads next anyway), orders them by parser in its own LDS slice (stable:
-// list order within a parser), then classifies them in that order, so the
-// wave mostly runs one parser's path instead of text and binary one after the
-// other.  The slice holds each entry's index, length, offset and connection
-// (16 bytes), so the classifying lane starts from the rule set and the
-// request's bytes instead of fetching the entry's metadata a second time.
+// sel: this protocol's entries (partition_kernel, mixed batches: ListEnt, the
+// index with the length, offset, rule set and flags), read coalesced; else
+// requests 0..n-1, whose entries the wave builds itself (mc_entries).  Each
+// wave takes kMcWaveChunk entries at a time, reads each one's parser from its
+// first byte (a line the classification reads next anyway), orders them by
+// parser in its own LDS slice (stable: list order within a parser), then
+// classifies them in that order, so the wave mostly runs one parser's path
+// instead of text and binary one after the other.  The slice holds the
+// entries, so the classifying lane starts from the rule set and the request's
+// bytes; it fetches the request's metadata itself only for a kEntByIndex entry.
 // Waves never wait for each other (no workgroup barrier).
 // work: the persistent grid's chunk counter (the launcher's call zeroes it):
 // after its first chunk a wave takes whichever chunk is next, so the grid's
 // waves end together; null: a fixed stride.
 template <bool kNfa, bool kLds, int kCh>
-__device__ __forceinline__ void mc_loop(Batch B, McTables T, const uint8_t *images, const uint32_t *__restrict__ sel,
-                                        const uint32_t *__restrict__ sel2, const uint32_t *__restrict__ sel_count,
+__device__ __forceinline__ void mc_loop(Batch B, McTables T, const uint8_t *images, const uint4 *__restrict__ sel,
+                                        const uint4 *__restrict__ sel2, const uint32_t *__restrict__ sel_count,
                                         uint32_t answer_other, uint4 *ent, uint32_t *__restrict__ work = nullptr) {
     const uint32_t n = B.n;
     // sel: sel_count[0] entries from sel's start, sel_count[1] from its end,
@@ -599,7 +591,8 @@ __device__ __forceinline__ void mc_loop(Batch B, McTables T, const uint8_t *imag
                     // first bytes would be one more round trip (zero-copy: over PCIe)
         const uint32_t i = lane;
         if (blockIdx.x == 0 && wave == 0 && i < m)
-            mc_one<kNfa, kLds, kCh>(B, T, images, !sel ? i : i < ma ? sel[i] : i < mb ? sel2[n - 1 - (i - ma)] : sel[n - 1 - (i - mb)],
+            mc_one<kNfa, kLds, kCh>(B, T, images,
+                                    !sel ? i : i < ma ? sel[i].x : i < mb ? sel2[n - 1 - (i - ma)].x : sel[n - 1 - (i - mb)].x,
                                     answer_other);
         return;
     }
@@ -613,14 +606,22 @@ __device__ __forceinline__ void mc_loop(Batch B, McTables T, const uint8_t *imag
         return (uint64_t)sweep + t < m ? sweep + t : m;  // (no wrap of the sum, nor of t: below m + one chunk per wave)
     };
     for (uint32_t base = (blockIdx.x * kMcWaves + wave) * kMcWaveChunk; base < m; base = next_chunk(base)) {
-        uint32_t ix[kMcSortPer], kd[kMcSortPer], ln[kMcSortPer], rsf[kMcSortPer];
-        uint64_t of[kMcSortPer];
+        uint32_t kd[kMcSortPer];
+        uint4 e[kMcSortPer];
+        if (sel) {
 #pragma unroll
-        for (int r = 0; r < kMcSortPer; r++) {
-            const uint32_t i = base + r * 64 + lane;
-            ix[r] = i >= m ? ~0u : !sel ? i : i < ma ? sel[i] : i < mb ? sel2[n - 1 - (i - ma)] : sel[n - 1 - (i - mb)];
+            for (int r = 0; r < kMcSortPer; r++) {
+                const uint32_t i = base + r * 64 + lane;
+                e[r] = i >= m ? make_uint4(~0u, 0, 0, kEntByIndex)
+                              : i < ma ? sel[i] : i < mb ? sel2[n - 1 - (i - ma)] : sel[n - 1 - (i - mb)];
+            }
+        } else {
+            uint32_t ix[kMcSortPer];
+#pragma unroll
+            for (int r = 0; r < kMcSortPer; r++) ix[r] = base + r * 64 + lane < m ? base + r * 64 + lane : ~0u;
+            mc_entries(B, ix, e);
         }
-        mc_kinds(B, T, ix, kd, of, ln, rsf);
+        mc_kinds(B, T, e, kd);
         uint32_t lo[4] = {0, 0, 0, 0};  // exclusive offsets, parser-major
 #pragma unroll
         for (int r = 0; r < kMcSortPer; r++)
@@ -631,7 +632,7 @@ __device__ __forceinline__ void mc_loop(Batch B, McTables T, const uint8_t *imag
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const uint64_t mk = __ballot(kd[r] == (uint32_t)k);
-                if (kd[r] == (uint32_t)k) slot[lo[k] + lanes_below(mk)] = make_uint4(ix[r], ln[r], (uint32_t)of[r], rsf[r]);
+                if (kd[r] == (uint32_t)k) slot[lo[k] + lanes_below(mk)] = e[r];
                 lo[k] += __popcll(mk);
             }
         }
@@ -640,13 +641,12 @@ __device__ __forceinline__ void mc_loop(Batch B, McTables T, const uint8_t *imag
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         for (uint32_t k = lane; k < total; k += 64) {
-            const uint4 e = slot[k];  // {index, length, offset low, offset high 10 bits | rule set << 12 | flags << 10}
-            if (e.w == ~0u) {
-                mc_one<kNfa, kLds, kCh>(B, T, images, e.x, answer_other);
+            const uint4 q = slot[k];
+            if (q.w == kEntByIndex) {
+                mc_one<kNfa, kLds, kCh>(B, T, images, q.x, answer_other);
             } else {
-                const DevConn conn{(int32_t)(e.w >> 12), PROTO_MEMCACHE, (uint8_t)((e.w >> 10) & 3u), 0xFFFF};
-                mc_body<kNfa, kLds, kCh>(B, T, images, e.x, (uint64_t)(e.w & 0x3FFu) << 32 | e.z, e.y, conn,
-                                         answer_other);
+                const DevConn conn{(int32_t)(q.w >> 12), PROTO_MEMCACHE, (uint8_t)((q.w >> 10) & 3u), 0xFFFF};
+                mc_body<kNfa, kLds, kCh>(B, T, images, q.x, l7_ent_off(q.z, q.w), q.y, conn, answer_other);
             }
         }
         __builtin_amdgcn_wave_barrier();  // (the slice is rewritten by the next chunk)
@@ -676,8 +676,8 @@ __device__ __forceinline__ bool mc_images_fit(const McTables &T) { return T.imag
 
 // work: mc_loop's.  prio: the wave priority the kernel runs at (0: as launched).
 template <bool kNfa, int kCh>
-__device__ __forceinline__ void mc_classify(Batch B, McTables T, const uint32_t *__restrict__ sel,
-                                            const uint32_t *__restrict__ sel2, const uint32_t *__restrict__ sel_count,
+__device__ __forceinline__ void mc_classify(Batch B, McTables T, const uint4 *__restrict__ sel,
+                                            const uint4 *__restrict__ sel2, const uint32_t *__restrict__ sel_count,
                                             uint32_t answer_other, uint32_t *__restrict__ work = nullptr,
                                             uint32_t prio = 0) {
     // (the instruction takes the level as an immediate)
@@ -738,8 +738,8 @@ __global__ __launch_bounds__(kBlock) void memcache_service_kernel(SvcBox *box, S
 // (the 4-chunk build holds 6 more registers: 4 waves per SIMD, where it does not spill)
 template <int kCh>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kCh == 1 ? kMcWavesPerSimd : 4, 8))) void memcache_classify_kernel(Batch B, McTables T,
-                                                                                  const uint32_t *__restrict__ sel,
-                                                                                  const uint32_t *__restrict__ sel2,
+                                                                                  const uint4 *__restrict__ sel,
+                                                                                  const uint4 *__restrict__ sel2,
                                                                                   const uint32_t *__restrict__ sel_count,
                                                                                   uint32_t answer_other,
                                                                                   uint32_t *__restrict__ work,
@@ -747,8 +747,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kCh == 1
     mc_classify<false, kCh>(B, T, sel, sel2, sel_count, answer_other, work, prio);
 }
 __global__ __launch_bounds__(kBlock) void memcache_classify_nfa_kernel(Batch B, McTables T,
-                                                                       const uint32_t *__restrict__ sel,
-                                                                       const uint32_t *__restrict__ sel2,
+                                                                       const uint4 *__restrict__ sel,
+                                                                       const uint4 *__restrict__ sel2,
                                                                        const uint32_t *__restrict__ sel_count,
                                                                        uint32_t answer_other) {
     mc_classify<true, kMcMaxChunks>(B, T, sel, sel2, sel_count, answer_other);
@@ -758,8 +758,8 @@ __global__ __launch_bounds__(kBlock) void memcache_classify_nfa_kernel(Batch B, 
 // last.  The kernels above, which large batches run, carry neither.
 template <bool kNfa, int kCh>
 __global__ __launch_bounds__(kBlock) void memcache_classify_sync_kernel(Batch B, McTables T,
-                                                                        const uint32_t *__restrict__ sel,
-                                                                        const uint32_t *__restrict__ sel2,
+                                                                        const uint4 *__restrict__ sel,
+                                                                        const uint4 *__restrict__ sel2,
                                                                         const uint32_t *__restrict__ sel_count,
                                                                         uint32_t answer_other, CopyIn ci) {
     copy_in_block(ci);
@@ -793,10 +793,11 @@ static uint32_t BesideBlocks(int per_cu) {
 // beside_slots > 0: the launch runs beside the Kafka kernel's persistent grid,
 // in that many workgroup slots per CU (LaunchKafkaClassify's leave_per_cu);
 // work: a word the call has zeroed, for the chunk counter of a persistent grid
-hipError_t LaunchMemcacheClassify(const Batch &B, const McTables &T, const uint32_t *sel, const uint32_t *sel2,
+hipError_t LaunchMemcacheClassify(const Batch &B, const McTables &T, const ListEnt *ents, const ListEnt *ents2,
                                   const uint32_t *sel_count, bool answer_other, uint32_t scratch_lanes,
                                   hipStream_t stream, const CopyIn *ci, int beside_slots, uint32_t *work) {
     if (B.n == 0) return hipSuccess;
+    const uint4 *sel = reinterpret_cast<const uint4 *>(ents), *sel2 = reinterpret_cast<const uint4 *>(ents2);
     // (cfg5, 20M entries: caps of 2048 / 4096 / 8192 / 16384 / 32768 / 131072
     // workgroups -> 3.62 / 3.39 / 3.26 / 3.21 / 3.25 / 3.72 ms; profiles/r5/ab5l_*)
     uint32_t blocks = (B.n + kBlock - 1) / kBlock;

@@ -14,7 +14,14 @@
 // produce from the api key: round 3 read each Kafka request's api key and each
 // memcached request's first byte, one HBM line per request, 5 of its 7 GB per
 // cfg5 launch; the memcached kernel now splits text from binary itself, from
-// bytes it reads anyway.  HTTP entries stay one list, but a block writes its
+// bytes it reads anyway.  The HTTP and memcached lists hold 16-byte entries
+// (ListEnt, device_tables.h): the index with the length, offset, rule set and
+// connection flags this kernel has loaded anyway, so a classifier's tile or
+// chunk starts from one coalesced load instead of the dependent chain list ->
+// conn_ids / offs / lens -> conns.  The Kafka lists stay index lists: eight
+// class lists of n slots each would be 128 B of scratch per request as
+// entries, and a Kafka group runs about 220 us per wave, so the same chain is
+// under 1 % of it.  HTTP entries stay one list, but a block writes its
 // HTTP entries length class by length class (round 6), so the HTTP kernel's
 // tiles hold requests of about one length (http_class below).  One block owns
 // 4096 consecutive requests (8 per lane, protocol kept in registers between
@@ -78,11 +85,13 @@ __device__ __forceinline__ uint8_t kafka_class(uint32_t len, uint32_t kind) {
 }
 }  // namespace
 
-// Lists: Kafka class c at sel_kafka + c * n; memcached text retrievals from
-// the start of sel_mc, binary requests from its end (n slots hold both); HTTP
-// from the start of sel_http, the other memcached text commands from its end;
-// counts[c] entries each (Kafka classes, memcached retrievals, memcached
-// binary, HTTP, other memcached text).  Within a
+// Lists: Kafka class c, request indices, at sel_kafka + c * n; memcached text
+// retrievals from the start of ent_mc, binary requests from its end (n entry
+// slots hold both); HTTP from the start of ent_http, the other memcached text
+// commands from its end; counts[c] entries each (Kafka classes, memcached
+// retrievals, memcached binary, HTTP, other memcached text).  An entry whose
+// request does not pack (l7_ent_word: no rule set, an offset past 2^42,
+// outside the arena) carries kEntByIndex and its index alone.  Within a
 // block's 4096 requests every list keeps stream order, so an HTTP tile of 64
 // list entries is, but for the tiles that straddle two blocks, a window of
 // the stream (the HTTP kernel's value-stop map streams that window).  Requests no classifier owns (unknown connection index, a
@@ -90,19 +99,19 @@ __device__ __forceinline__ uint8_t kafka_class(uint32_t len, uint32_t kind) {
 // consumed 0, so every request of the batch gets a verdict whichever
 // classifiers run (the HTTP kernel is then told not to answer them again).
 __global__ __launch_bounds__(kBlock) void partition_kernel(Batch B, uint32_t *__restrict__ sel_kafka,
-                                                           uint32_t *__restrict__ sel_mc,
-                                                           uint32_t *__restrict__ sel_http,
+                                                           uint4 *__restrict__ ent_mc, uint4 *__restrict__ ent_http,
                                                            uint32_t *__restrict__ counts) {
     const uint32_t n = B.n;
     __shared__ uint32_t s_off[kWaves][kClasses];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t start = (uint64_t)blockIdx.x * (kBlock * kPer);
     const uint64_t below = (1ull << lane) - 1;
-    uint8_t p[kPer];  // class + 1, 0 = none
+    static_assert(kClasses < 16 && kPer == 8, "a row's class + 1 in four bits of one word");
+    uint32_t p = 0;  // class + 1 of row r in bits 4r .. 4r + 3, 0 = none
     uint32_t cnt[kClasses] = {};
     // The rows' loads go out phase by phase (connection ids, connections,
-    // Kafka lengths, offsets, api keys), so a block waits five memory
-    // latencies, not five per row.
+    // lengths, offsets, api keys), so a block waits five memory latencies, not
+    // five per row.
     uint32_t ci[kPer], pw[kPer];
 #pragma unroll
     for (int r = 0; r < kPer; r++) {
@@ -110,34 +119,46 @@ __global__ __launch_bounds__(kBlock) void partition_kernel(Batch B, uint32_t *__
         ci[r] = idx < n ? B.conn_ids[idx] : 0xFFFFFFFFu;
     }
 #pragma unroll
-    for (int r = 0; r < kPer; r++) {  // proto | flags << 8 of the connection, PROTO_NONE if unknown
-        pw[r] = PROTO_NONE;
+    for (int r = 0; r < kPer; r++) {  // the connection's proto (PROTO_NONE if unknown) in bits 0..7 of its entry head
+        pw[r] = l7_ent_head(-1, 0) | PROTO_NONE;
         if (ci[r] < B.nconns) {
             const DevConn c = B.conns[ci[r]];
-            pw[r] = (uint32_t)c.proto | (uint32_t)c.flags << 8;
+            pw[r] = l7_ent_head(c.ruleset, c.flags) | (uint32_t)c.proto;
         }
     }
-    // Kafka: the length; the offset only where the api key is read (the
-    // classes are scheduling: the Kafka kernel checks every request's bytes
-    // against the arena itself)
+    // The length of every listed request.  The offset: of HTTP and memcached
+    // requests, for their entries; of a Kafka request only where the api key
+    // is read (the classes are scheduling: the Kafka kernel checks every
+    // request's bytes against the arena itself).
     uint32_t len[kPer];
 #pragma unroll
     for (int r = 0; r < kPer; r++) {
         const uint64_t idx = start + (uint64_t)r * kBlock + threadIdx.x;
-        len[r] = (pw[r] & 0xFF) == PROTO_KAFKA || (pw[r] & 0xFF) == PROTO_HTTP ? B.lens[idx] : 0;
+        const uint32_t proto = pw[r] & 0xFF;
+        len[r] = proto == PROTO_KAFKA || proto == PROTO_HTTP || proto == PROTO_MEMCACHE ? B.lens[idx] : 0;
     }
     uint64_t off[kPer];
+    bool amb[kPer];  // a Kafka request whose length does not settle its class
 #pragma unroll
     for (int r = 0; r < kPer; r++) {
         const uint64_t idx = start + (uint64_t)r * kBlock + threadIdx.x;
-        off[r] = (pw[r] & 0xFF) == PROTO_KAFKA && len[r] >= kKafkaAmbLo && len[r] < kKafkaAmbHi ? B.offs[idx] : ~0ull;
+        const uint32_t proto = pw[r] & 0xFF;
+        amb[r] = proto == PROTO_KAFKA && len[r] >= kKafkaAmbLo && len[r] < kKafkaAmbHi;
+        off[r] = amb[r] || proto == PROTO_HTTP || proto == PROTO_MEMCACHE ? B.offs[idx] : ~0ull;
     }
     uint32_t kd[kPer];  // Kafka api key where the length does not settle the class
 #pragma unroll
     for (int r = 0; r < kPer; r++) {
         kd[r] = 0xFFFFu;
-        if (off[r] != ~0ull && l7_in_arena(off[r], len[r], B.arena_len))
+        if (amb[r] && l7_in_arena(off[r], len[r], B.arena_len))
             kd[r] = (uint32_t)B.arena[off[r] + 4] << 8 | B.arena[off[r] + 5];
+    }
+    // words z and w of the HTTP and memcached entries (ListEnt, device_tables.h)
+    uint32_t ez[kPer], ew[kPer];
+#pragma unroll
+    for (int r = 0; r < kPer; r++) {
+        ez[r] = (uint32_t)off[r];
+        ew[r] = l7_ent_word(pw[r], off[r], len[r], B.arena_len);
     }
 #pragma unroll
     for (int r = 0; r < kPer; r++) {
@@ -158,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void partition_kernel(Batch B, uint32_t *__
                 B.consumed[idx] = 0;
             }
         }
-        p[r] = cls;
+        p |= (uint32_t)cls << (4 * r);
 #pragma unroll
         for (int c = 0; c < kClasses; c++) cnt[c] += __popcll(__ballot(cls == c + 1));
     }
@@ -196,14 +217,16 @@ __global__ __launch_bounds__(kBlock) void partition_kernel(Batch B, uint32_t *__
         const uint32_t idx = (uint32_t)(start + (uint64_t)r * kBlock + threadIdx.x);
 #pragma unroll
         for (int c = 0; c < kClasses; c++) {
-            const uint64_t mk = __ballot(p[r] == c + 1);
-            if (p[r] == c + 1) {
+            const bool here = ((p >> (4 * r)) & 15u) == (uint32_t)(c + 1);
+            const uint64_t mk = __ballot(here);
+            if (here) {
                 const uint32_t pos = lo[c] + __popcll(mk & below);
+                const uint4 e = make_uint4(idx, len[r], ez[r], ew[r]);
                 if (c < kKafkaClasses) sel_kafka[(size_t)c * n + pos] = idx;
-                else if (c == kMcText) sel_mc[pos] = idx;
-                else if (c == kMcBinary) sel_mc[n - 1 - pos] = idx;  // binary from the list's end
-                else if (c == kMcText2) sel_http[n - 1 - pos] = idx;  // other text commands from the HTTP list's end
-                else sel_http[pos] = idx;
+                else if (c == kMcText) ent_mc[pos] = e;
+                else if (c == kMcBinary) ent_mc[n - 1 - pos] = e;  // binary from the list's end
+                else if (c == kMcText2) ent_http[n - 1 - pos] = e;  // other text commands from the HTTP list's end
+                else ent_http[pos] = e;
             }
             lo[c] += __popcll(mk);
         }
@@ -211,11 +234,12 @@ __global__ __launch_bounds__(kBlock) void partition_kernel(Batch B, uint32_t *__
 }
 
 // counts[0..kKafkaClasses + 4) must be zero on entry (the caller clears them on `stream`).
-hipError_t LaunchPartition(const Batch &B, uint32_t *sel_kafka, uint32_t *sel_mc, uint32_t *sel_http, uint32_t *counts,
+hipError_t LaunchPartition(const Batch &B, uint32_t *sel_kafka, ListEnt *ent_mc, ListEnt *ent_http, uint32_t *counts,
                            hipStream_t stream) {
     if (B.n == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((uint64_t)B.n + kBlock * kPer - 1) / (kBlock * kPer));
-    hipLaunchKernelGGL(partition_kernel, dim3(blocks), dim3(kBlock), 0, stream, B, sel_kafka, sel_mc, sel_http, counts);
+    hipLaunchKernelGGL(partition_kernel, dim3(blocks), dim3(kBlock), 0, stream, B, sel_kafka,
+                       reinterpret_cast<uint4 *>(ent_mc), reinterpret_cast<uint4 *>(ent_http), counts);
     return hipGetLastError();
 }
 

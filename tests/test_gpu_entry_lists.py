@@ -1,0 +1,209 @@
+"""The partition's packed list entries (ListEnt, device_tables.h) and their
+readers: the HTTP tile kernel, the small-call HTTP kernel, the memcached
+kernel and the grouping kernels.
+
+One engine serves HTTP (a hot rule set and a cold one, so the general HTTP
+kernel runs from entries too), Kafka and memcached, so every call is
+partitioned whatever its size.  One shuffled stream of 8192 + 17 requests is
+classified by the oracle once; every case classifies a prefix (or a tiling)
+of it on the device and compares verdict, rule id and consumed length.
+
+The stream holds, among ordinary requests and therefore in the same tiles and
+chunks: HTTP lengths on both sides of every length-class boundary (703/704,
+1151/1152, 1599/1600); memcached text retrievals, other text commands and
+binary requests on connections whose flags force the text parser, force the
+binary one, or leave it to the first byte; connection ids past the table; a
+connection without a parser (the only kind whose rule set is -1: a
+connection of an owned protocol that resolves to no rule set is refused by
+set_connections); empty requests on an HTTP and on a memcached connection.
+Requests outside the arena are made per call (the oracle cannot read them):
+their answer is UNSUPPORTED, rule -1, consumed 0."""
+import numpy as np
+import pytest
+import torch
+
+from cilium_amd import api, gen
+from cilium_amd._lib import ALLOW, DENY, PROTO_HTTP, PROTO_MEMCACHE, UNSUPPORTED
+from test_gpu_http import assert_same
+
+pytestmark = pytest.mark.gpu
+
+N = 8192 + 17
+SIZES = [1, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, N]
+HTTP_LENS = [703, 704, 1151, 1152, 1599, 1600, 120, 300, 900, 1300, 2040]
+
+
+def _http_request(k):
+    total = HTTP_LENS[k % len(HTTP_LENS)]
+    head = b"%s /api/v%d/svc%d/x HTTP/1.1\r\nHost: svc-%d.x\r\n" % ([b"GET", b"POST", b"PUT"][k % 3], k % 3 + 1, k % 16,
+                                                                 k % 16)
+    r = head + b"X-Pad: " + gen._PAD[:total - len(head) - 11] + b"\r\n\r\n"
+    assert len(r) == total
+    return r
+
+
+def _stream():
+    """The mixed stream, its connections and policy."""
+    nh, nk = 3700, 2000
+    nm = N - nh - nk - 200  # 200 special requests
+    # HTTP: remote 256 on four connections (the hot rule set), 257 on two (cold)
+    groups = [api.port_rule(remote_policies=[256 + g], http=api.http_rules_from_api(gen.cfg2_rules(8 * g, 8)))
+              for g in range(2)]
+    hpol = api.policy_set(api.network_policy("10.0.0.1", 3, ingress=[(80, groups)]))
+    hconns = gen.make_conns(6, 0, 80, True, PROTO_HTTP, np.array([256, 256, 256, 256, 257, 257]))
+    hreqs = [_http_request(k) for k in range(nh)]
+    k = gen.kafka_workload(nk, seed=gen.SEED_BASE + 71)
+    m = gen.memcache_workload(nm, seed=gen.SEED_BASE + 73)
+    mconns = m.conns.copy()
+    mconns["flags"] = np.arange(len(mconns)) % 3  # by first byte / text / binary
+    pconn = gen.make_conns(1, 0, 80, True, 0, [256])  # no parser
+    conns = np.concatenate([hconns, k.conns, mconns, pconn])
+    ch, ck, cm = len(hconns), len(k.conns), len(mconns)
+    conns["policy"][ch:ch + ck] = 1
+    conns["policy"][ch + ck:ch + ck + cm] = 2
+    pol = {"policies": [hpol["policies"][0], dict(k.policy["policies"][0], name="10.0.0.2"), m.policy["policies"][0]]}
+    kbuf, mbuf = k.arena.tobytes(), m.arena.tobytes()
+    reqs = hreqs + [kbuf[int(o):int(o) + int(l)] for o, l in zip(k.offsets, k.lengths)] + \
+        [mbuf[int(o):int(o) + int(l)] for o, l in zip(m.offsets, m.lengths)]
+    # (method, version and service repeat every 48 requests: each such run on one connection)
+    cids = np.concatenate([np.arange(nh) // 48 % 6, k.conn_ids + ch, m.conn_ids + ch + ck]).astype(np.uint32)
+    # the special requests: copies of ordinary ones on other connections, and empty ones
+    nconn = len(conns)
+    sp_reqs, sp_cids = [], []
+    for j in range(200):
+        kind = j % 5
+        src = hreqs[j] if j % 2 else reqs[nh + nk + j]
+        if kind == 0:
+            sp_reqs.append(src); sp_cids.append(nconn + j)          # past the connection table
+        elif kind == 1:
+            sp_reqs.append(src); sp_cids.append(0xFFFFFFFF - j)
+        elif kind == 2:
+            sp_reqs.append(src); sp_cids.append(nconn - 1)          # the parserless connection
+        elif kind == 3:
+            sp_reqs.append(b""); sp_cids.append(j % 6)              # empty, HTTP (hot and cold)
+        else:
+            sp_reqs.append(b""); sp_cids.append(ch + ck + j % cm)   # empty, memcached (every flag)
+    reqs += sp_reqs
+    cids = np.concatenate([cids, np.array(sp_cids, np.uint32)])
+    assert len(reqs) == N
+    perm = np.random.default_rng(gen.SEED_BASE + 79).permutation(N)
+    arena, offs, lens = gen.pack([reqs[i] for i in perm])
+    return gen.Workload("entry-lists", arena, offs, lens, cids[perm], conns, pol)
+
+
+class _Ctx:
+    pass
+
+
+@pytest.fixture(scope="module")
+def ctx(engine, oracle):
+    c = _Ctx()
+    c.w = w = _stream()
+    c.ref = oracle.classify_workload(w, 8)
+    engine.update_policy(w.policy)
+    engine.set_connections(w.conns)
+    c.engine = engine
+    c.dev = torch.device("cuda", 0)
+    c.d_arena = torch.from_numpy(w.arena).to(c.dev)
+    nc = len(w.conns)
+    known = w.conn_ids < nc
+    c.proto = np.where(known, w.conns["proto"][np.minimum(w.conn_ids, nc - 1)], 0)
+    c.flags = np.where(known, w.conns["flags"][np.minimum(w.conn_ids, nc - 1)], 0)
+    return c
+
+
+def _run(c, arena_t, offs, lens, cids):
+    n = len(offs)
+    d_off = torch.from_numpy(np.ascontiguousarray(offs, np.uint64).view(np.int64)).to(c.dev)
+    d_len = torch.from_numpy(np.ascontiguousarray(lens, np.uint32).view(np.int32)).to(c.dev)
+    d_cid = torch.from_numpy(np.ascontiguousarray(cids, np.uint32).view(np.int32)).to(c.dev)
+    out = [torch.full((n,), 7, dtype=t, device=c.dev) for t in (torch.uint8, torch.int32, torch.int32)]
+    torch.cuda.synchronize()
+    c.engine.classify_device(arena_t.data_ptr(), arena_t.numel(), d_off.data_ptr(), d_len.data_ptr(), d_cid.data_ptr(),
+                             n, *[t.data_ptr() for t in out])
+    torch.cuda.synchronize()
+    return out[0].cpu().numpy(), out[1].cpu().numpy(), out[2].cpu().numpy().view(np.uint32)
+
+
+def test_stream_covers_the_cases(ctx):
+    """The stream is what the docstring says (host-side checks of the fixture)."""
+    w, ref, proto, flags = ctx.w, ctx.ref, ctx.proto, ctx.flags
+    http, mc = proto == PROTO_HTTP, proto == PROTO_MEMCACHE
+    for L in (703, 704, 1151, 1152, 1599, 1600):
+        assert (w.lengths[http] == L).any(), L
+    cold = http & (w.conn_ids >= 4)
+    for sel in (http & ~cold, cold):
+        assert (ref[0][sel] == ALLOW).any() and (ref[0][sel] == DENY).any()
+    first = np.where(w.lengths > 0, w.arena[np.minimum(w.offsets, len(w.arena) - 1).astype(np.int64)], 0)
+    for f in (0, 1, 2):  # every parser choice meets text retrievals, other text and binary requests
+        s = mc & (flags == f) & (w.lengths > 0)
+        assert (first[s] == ord("g")).any() and (first[s] >= 0x80).any() and ((first[s] < 0x80) & (first[s] != ord("g"))).any()
+    assert (ref[0][mc] == ALLOW).any() and (ref[0][mc] == DENY).any()
+    assert (http & (w.lengths == 0)).any() and (mc & (w.lengths == 0)).any()
+    assert (w.conn_ids >= len(w.conns)).sum() >= 40 and (w.conn_ids == len(w.conns) - 1).sum() >= 20
+    nmc = [int(mc[:n].sum()) for n in SIZES]
+    assert any(0 < x <= 64 for x in nmc) and any(x > 64 for x in nmc), nmc  # both memcached paths
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_prefix_matches_oracle(ctx, n):
+    w = ctx.w
+    got = _run(ctx, ctx.d_arena, w.offsets[:n], w.lengths[:n], w.conn_ids[:n])
+    assert_same(got, tuple(r[:n] for r in ctx.ref), w)
+
+
+@pytest.mark.parametrize("n", [257, 4097, N])
+def test_requests_outside_the_arena(ctx, n):
+    """Entries by index among packed ones: every 13th request of an owned
+    protocol leaves the arena (starts past it, runs past it, an offset past
+    2^42, one past 2^62)."""
+    w = ctx.w
+    offs, lens = w.offsets[:n].copy(), w.lengths[:n].copy()
+    ref = [r[:n].copy() for r in ctx.ref]
+    bad = np.nonzero(ctx.proto[:n] != 0)[0][::13]
+    A = len(w.arena)
+    for j, i in enumerate(bad):
+        if j % 4 == 0:
+            offs[i] = A + 4096
+        elif j % 4 == 1:
+            offs[i], lens[i] = A - 1, 2
+        elif j % 4 == 2:
+            offs[i] = (1 << 42) + int(offs[i])
+        else:
+            offs[i] = 1 << 62
+    ref[0][bad], ref[1][bad], ref[2][bad] = UNSUPPORTED, -1, 0
+    assert len(bad) >= 15 and len({int(p) for p in ctx.proto[:n][bad]}) == 3
+    got = _run(ctx, ctx.d_arena, offs, lens, w.conn_ids[:n])
+    assert_same(got, tuple(ref), w)
+
+
+def test_offsets_above_4_gib(ctx):
+    """Offset bits 32..41 of an entry: the HTTP and memcached requests of the
+    stream's first 1024, placed above the 4 GiB mark of a buffer of
+    4 GiB + 1 MiB (allocated, not filled), answer as they do placed low."""
+    w = ctx.w
+    idx = np.nonzero((ctx.proto[:1024] == PROTO_HTTP) | (ctx.proto[:1024] == PROTO_MEMCACHE))[0]
+    s = gen.select(w, idx)
+    assert 300 <= s.n and len(s.arena) < (1 << 20) - 4096
+    HI = (1 << 32) + 4096 + 3
+    big = torch.empty((1 << 32) + (1 << 20), dtype=torch.uint8, device=ctx.dev)
+    src = torch.from_numpy(s.arena.copy()).to(ctx.dev)
+    big[:len(s.arena)] = src
+    big[HI:HI + len(s.arena)] = src
+    low = _run(ctx, big, s.offsets, s.lengths, s.conn_ids)
+    high = _run(ctx, big, s.offsets + np.uint64(HI), s.lengths, s.conn_ids)
+    ref = tuple(r[idx] for r in ctx.ref)
+    assert (ref[0] == ALLOW).any() and (ref[0] == DENY).any()
+    assert_same(low, ref, s)
+    assert_same(high, ref, s)
+
+
+def test_grouped_path(ctx):
+    """kGroupMin = 65,536 requests with a cold rule set in use: the grouping
+    kernels read the HTTP entries (the stream tiled eight times over one arena)."""
+    w = ctx.w
+    n = 65536 + 17
+    idx = np.arange(n) % N
+    got = _run(ctx, ctx.d_arena, w.offsets[idx], w.lengths[idx], w.conn_ids[idx])
+    assert_same(got, tuple(r[idx] for r in ctx.ref), gen.Workload("t", w.arena, w.offsets[idx], w.lengths[idx],
+                                                                  w.conn_ids[idx], w.conns, w.policy))
