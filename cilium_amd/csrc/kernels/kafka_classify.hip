@@ -75,7 +75,10 @@ struct GRd {
     }
     // little-endian 4 bytes at byte rel (rel + 4 <= 64) of the staged chunks
     __device__ __forceinline__ uint32_t slot_le4(uint32_t rel) {
-        const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * (threadIdx.x & 63));
+        // (the addresses are formed here, at the read: hoisted out of the message loops they were
+        // two more values held across the CRC, and spilled)
+        asm volatile("" : "+v"(rel));
+        const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * lane_id());
         const uint32_t w0 = rel >> 2, w1 = w0 < 15 ? w0 + 1 : 15;
         uint32_t lo, hi;
         asm volatile("s_waitcnt vmcnt(0)\n\tds_read_b32 %0, %2\n\tds_read_b32 %1, %3\n\ts_waitcnt lgkmcnt(0)"
@@ -109,7 +112,7 @@ struct GRd {
         {
             hlim = 0;  // the head leaves the slot
             crc_stage(stage, reinterpret_cast<const uint8_t *>(c0), lastc);
-            const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * (threadIdx.x & 63));
+            const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * lane_id());
             uint4 v0, v1, v2, v3;
             asm volatile("s_waitcnt vmcnt(0)\n\t"
                          "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\t"
@@ -477,19 +480,23 @@ __device__ __forceinline__ int32_t str_lookup(const DevStrSlot *tab, uint32_t ma
 }
 
 struct ReqInfo {
-    int kind;
-    int version;
-    int typed;      // 0 nil request, 1 typed with topics/ClientID, 2 ConsumerMetadata
+    // One word, not three: kind, version and the typed class were three registers held across the walk
+    // and its CRCs, and at 6 waves per SIMD (80 VGPRs) three spilled ones.  Each use extracts its field.
+    uint32_t kv;    // kind << 16 | version (both int16, as on the wire)
     int32_t client; // interned id, -2 unknown / empty
+    __device__ __forceinline__ int kind_() const { return (int)(int16_t)(kv >> 16); }
+    __device__ __forceinline__ int version_() const { return (int)(int16_t)(kv & 0xFFFF); }
+    // 0 nil request, 1 typed with topics/ClientID, 2 ConsumerMetadata
+    __device__ __forceinline__ int typed_() const { return kind_typed(kind_()); }
 };
 
 __device__ __forceinline__ bool rule_matches(const DevKafkaRule &r, const ReqInfo &q) {
-    if (!r.any_key && (q.kind < 0 || q.kind > 63 || !((r.keymask >> q.kind) & 1))) return false;
-    if (r.has_version && r.version != q.version) return false;
+    if (!r.any_key && (q.kind_() < 0 || q.kind_() > 63 || !((r.keymask >> q.kind_()) & 1))) return false;
+    if (r.has_version && r.version != q.version_()) return false;
     if (!r.has_topic && r.client < 0) return true;
-    if (q.typed == 1) return r.client < 0 || r.client == q.client;
-    if (q.typed == 2) return true;
-    return !(r.has_topic && is_topic_api_key(q.kind));
+    if (q.typed_() == 1) return r.client < 0 || r.client == q.client;
+    if (q.typed_() == 2) return true;
+    return !(r.has_topic && is_topic_api_key(q.kind_()));
 }
 
 // first position of topic `tid`'s rule list that matches, kInf if none
@@ -537,7 +544,7 @@ __device__ __forceinline__ uint32_t matches_rule(const KafkaTables &T, const Dev
                                                  uint32_t ntopics, uint32_t cmax) {
     uint32_t best = kInf;
     if (ntopics == 0) {
-        const int key = (q.kind >= 0 && q.kind < 64) ? q.kind : 64;
+        const int key = (q.kind_() >= 0 && q.kind_() < 64) ? q.kind_() : 64;
         const uint32_t off = T.index[rs.bykey_off + 2 * key], cnt = T.index[rs.bykey_off + 2 * key + 1];
         for (uint32_t i = 0; i < cnt; i++) {
             const uint32_t p = T.index[off + i];
@@ -577,7 +584,7 @@ struct ExactHooks {
         if (q.client < 0) q.client = -2;
     }
     __device__ __forceinline__ void topic(uint32_t o, uint32_t l) {
-        if (q.typed != 1) return;
+        if (q.typed_() != 1) return;
         if constexpr (!std::is_same<L, NoTopicLog>::value) {
             // GetTopics(): every topic in wire order, duplicates kept; the row holds the first `stride`
             if (ntopics < log.stride) log.row[ntopics] = LogSpan{o, l};
@@ -625,7 +632,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
     __shared__ uint32_t crctab[kCrcTables * 256];
     // per wave: the CRC's 64-byte-per-lane staging area (crc32_ieee_staged)
     __shared__ __attribute__((aligned(16))) uint8_t crcstage[kBlock / 64][4096];
-    uint8_t *stage = crcstage[threadIdx.x >> 6];
+    // (the wave's index as a scalar: the slot's address stays in scalar registers, not in a VGPR per lane)
+    uint8_t *stage = crcstage[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
     crc_tables_init(crctab, threadIdx.x);
     // (L7_KAFKA_CLASSES length classes, class c at sel + c * n, sel_count[c] entries each)
     constexpr int kCls = L7_KAFKA_CLASSES;
@@ -649,7 +657,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
     const uint32_t stride = main_sweep ? main_sweep : gridDim.x * kBlock;
     auto next_entry = [&](uint32_t i) -> uint32_t {
         if (!work) return i + stride;
-        const uint32_t lane = threadIdx.x & 63;
+        const uint32_t lane = lane_id();
         uint32_t t = 0;
         if (lane == (uint32_t)__builtin_amdgcn_readfirstlane(lane)) t = atomicAdd(work, 64u);
         return stride + __builtin_amdgcn_readfirstlane(t) + lane;
@@ -699,9 +707,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
             if (rawlen > len) { verdict = V_INCOMPLETE; break; }
             if (rawlen < 12) break;
             ReqInfo q;
-            q.kind = (int16_t)r.be(4, 2);
-            q.version = (int16_t)r.be(6, 2);
-            q.typed = kind_typed(q.kind);
+            q.kv = (uint32_t)r.be(4, 4);  // (rawlen >= 12: both fields)
             q.client = -2;
             // fields are read where they are used: a copy would hold 9 VGPRs across the decode
             const DevKafkaRuleset &rs = T.rulesets[conn.ruleset];
@@ -709,14 +715,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
             Log lg{};
             if constexpr (kLog) lg = TopicLog{ltopics + (size_t)idx * lstride, lstride};
             ExactHooks<Log> h{T, rs, q, r, crctab, stage, 0, 0, lg};
-            if (q.typed && kafka_walk(r, rawlen, q.kind, zflag, h) == -1) break;
+            if (q.typed_() && kafka_walk(r, rawlen, q.kind_(), zflag, h) == -1) break;
             consumed = rawlen;
             verdict = V_DENY;
             if constexpr (kLog) {
                 const uint32_t corr = (uint32_t)r.be(8, 4);  // (rawlen >= 12)
                 uint4 *o = reinterpret_cast<uint4 *>(lrec + idx);
-                o[0] = make_uint4(LOG_KAFKA | (h.ntopics > lstride ? 0x100u : 0u) | ((uint32_t)(uint16_t)q.kind << 16),
-                                  (uint32_t)(uint16_t)q.version, corr, h.ntopics);
+                // (kind in the upper half of word 0, version in word 1, each as its 16 wire bits)
+                o[0] = make_uint4(LOG_KAFKA | (h.ntopics > lstride ? 0x100u : 0u) | (q.kv & 0xFFFF0000u),
+                                  q.kv & 0xFFFFu, corr, h.ntopics);
                 o[1] = make_uint4(0, 0, 0, 0);
             }
             if (!rs.any) break;

@@ -40,6 +40,11 @@ __device__ __forceinline__ uint32_t crc_slice8(const uint32_t *tab, uint32_t lo,
            tab[1 * 256 + ((hi >> 16) & 0xFF)] ^ tab[hi >> 24];
 }
 constexpr uint32_t kInf = 0xFFFFFFFFu;
+// the lane within its wave (one-dimensional workgroups of whole waves), from the wave's own count:
+// threadIdx.x need not stay live for it
+__device__ __forceinline__ uint32_t lane_id() {
+    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+}
 
 // Per-lane byte cursor: the decoders walk their request forward, so each lane
 // keeps the 16-byte aligned chunk it last touched in registers and serves
@@ -306,7 +311,7 @@ __device__ __forceinline__ void crc_stage(uint8_t *stage, const uint8_t *q, uint
 // one staged 64-byte batch hashed into c; the next one (if any) staged meanwhile
 __device__ __forceinline__ uint32_t crc_batch(const uint32_t *tab, uint8_t *stage, uint32_t c, const uint8_t *next,
                                               uintptr_t lastc) {
-    const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * (threadIdx.x & 63));
+    const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * lane_id());
     uint4 v0, v1, v2, v3;
     asm volatile("s_waitcnt vmcnt(0)\n\t"
                  "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\t"
@@ -334,7 +339,7 @@ __device__ __forceinline__ uint32_t lds_word_at(uint32_t la, uint32_t j) {  // b
 // (bytes [j0, rem) of the slot: j0 a multiple of 8)
 __device__ __forceinline__ uint32_t crc_last(uint32_t tabaddr, uint8_t *stage, uint32_t rem, uint32_t c,
                                              uint32_t j0 = 0) {
-    const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * (threadIdx.x & 63));
+    const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * lane_id());
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     uint32_t j = j0;
     for (; j + 8 <= rem; j += 8) {
@@ -385,7 +390,7 @@ __device__ __forceinline__ uint32_t crc32_ieee_window(const uint32_t *tab, Cur &
         const uint8_t *c0 = reinterpret_cast<const uint8_t *>((uintptr_t)(p - 16) & ~(uintptr_t)15);
         const uint32_t o = (uint32_t)((p + i) - c0);  // 16 or 32
         if (n - i <= 64 - o) return ~crc_last(tabaddr, stage, o + (n - i), c, o);
-        const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * (threadIdx.x & 63));
+        const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * lane_id());
         uint4 v1, v2, v3;
         asm volatile("ds_read_b128 %0, %3 offset:1024\n\tds_read_b128 %1, %3 offset:2048\n\t"
                      "ds_read_b128 %2, %3 offset:3072\n\ts_waitcnt lgkmcnt(0)"
