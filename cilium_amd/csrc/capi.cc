@@ -163,7 +163,7 @@ int SwapIn(l7g_engine *e, std::unique_ptr<PolicySet> ps, std::unique_ptr<HttpCom
 // stays in force (an NPDS NACK).  Caller holds e->mu.
 int PolicySwap(l7g_engine *e, std::unique_ptr<PolicySet> ps, char *err, size_t errlen) {
     auto hc = std::make_unique<HttpCompiler>(ps.get());
-    auto kc = std::make_unique<KafkaCompiler>(ps.get());
+    auto kc = std::make_unique<KafkaCompiler>(ps.get(), e->kafka_dense_budget);
     auto mc = std::make_unique<McCompiler>(ps.get());
     auto r2 = std::make_unique<R2Compiler>(ps.get());
     auto cs = std::make_unique<CassCompiler>(ps.get());
@@ -365,7 +365,11 @@ l7g_engine *l7g_engine_create(int device, char *err, size_t errlen) {
     e->svc_on = !(v && v[0] == '0');
     e->ps = std::make_unique<PolicySet>();
     e->hc = std::make_unique<HttpCompiler>(e->ps.get());
-    e->kc = std::make_unique<KafkaCompiler>(e->ps.get());
+    // L7G_KAFKA_DENSE_BUDGET=<words>: the Kafka compiler's dense-table budget (tests of the
+    // sorted-directory form of a rule set; unset, kDenseTopicBudget)
+    if (const char *b = getenv("L7G_KAFKA_DENSE_BUDGET"); b && b[0] >= '0' && b[0] <= '9')
+        e->kafka_dense_budget = (size_t)strtoull(b, nullptr, 10);
+    e->kc = std::make_unique<KafkaCompiler>(e->ps.get(), e->kafka_dense_budget);
     e->mc = std::make_unique<McCompiler>(e->ps.get());
     e->r2 = std::make_unique<R2Compiler>(e->ps.get());
     e->cs = std::make_unique<CassCompiler>(e->ps.get());
@@ -441,7 +445,7 @@ int l7g_tables_import(l7g_engine *e, const uint8_t *buf, size_t len, char *err, 
                          : LoadPolicySet(src.data(), src.size(), ps.get(), &m);
     if (!ok) { set_err(err, errlen, m); return -1; }
     auto hc = std::make_unique<HttpCompiler>(ps.get());
-    auto kc = std::make_unique<KafkaCompiler>(ps.get());
+    auto kc = std::make_unique<KafkaCompiler>(ps.get(), e->kafka_dense_budget);
     auto mc = std::make_unique<McCompiler>(ps.get());
     auto r2 = std::make_unique<R2Compiler>(ps.get());
     auto cs = std::make_unique<CassCompiler>(ps.get());

@@ -44,7 +44,7 @@ void BuildHash(const std::unordered_map<std::string, int> &ids, std::vector<uint
 }
 }  // namespace
 
-KafkaCompiler::KafkaCompiler(const PolicySet *ps) : ps_(ps) {
+KafkaCompiler::KafkaCompiler(const PolicySet *ps, size_t dense_budget) : ps_(ps), dense_budget_(dense_budget) {
     for (auto &np : ps->policies)
         for (auto *dir : {&np.ingress, &np.egress})
             for (auto &pp : *dir)
@@ -101,8 +101,6 @@ int KafkaCompiler::RulesetFor(int policy, bool ingress, uint32_t port, uint64_t 
     return id;
 }
 
-static constexpr size_t kDenseTopicBudget = size_t(64) << 20;  // u32 entries in index[] (256 MiB)
-
 int KafkaCompiler::Compile(const std::vector<const KafkaRule *> &rules, bool any) {
     compiled++;
     KafkaImage &I = img_;
@@ -152,7 +150,7 @@ int KafkaCompiler::Compile(const std::vector<const KafkaRule *> &rules, bool any
     // rule decides -- is one table read after the topic's hash probe.
     rs.tdense_off = ~0u;
     constexpr size_t kEntU32 = sizeof(DevKafkaTopicEnt) / 4;
-    if (!by_topic.empty() && I.index.size() + 3 + kEntU32 * I.ntopics <= kDenseTopicBudget) {
+    if (!by_topic.empty() && I.index.size() + 3 + kEntU32 * I.ntopics <= dense_budget_) {
         I.index.resize((I.index.size() + 3) & ~(size_t)3, 0);
         rs.tdense_off = (uint32_t)I.index.size();
         I.index.resize(I.index.size() + kEntU32 * I.ntopics, 0);

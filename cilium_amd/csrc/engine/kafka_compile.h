@@ -37,9 +37,13 @@ struct KafkaImage {
     size_t ntopics = 0;
 };
 
+// u32 entries of index[] (256 MiB) up to which a rule set gets the dense
+// per-topic table; past it a rule set keeps to its sorted directory
+constexpr size_t kDenseTopicBudget = size_t(64) << 20;
+
 class KafkaCompiler {
 public:
-    explicit KafkaCompiler(const PolicySet *ps);
+    explicit KafkaCompiler(const PolicySet *ps, size_t dense_budget = kDenseTopicBudget);
     // proxylib: the proxylib "kafka" parser's view of the port entries
     int RulesetFor(int policy, bool ingress, uint32_t port, uint64_t src_id, bool proxylib, std::string *err);
     const KafkaImage &image() const { return img_; }
@@ -70,6 +74,7 @@ public:
 
 private:
     const PolicySet *ps_;
+    size_t dense_budget_;
     KafkaImage img_;
     std::unordered_map<std::string, int> topic_id_, client_id_;
     std::map<std::pair<std::vector<int>, int>, int> cache_;

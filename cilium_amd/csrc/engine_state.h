@@ -202,6 +202,9 @@ struct l7g_engine {
     std::unique_ptr<PolicySet> ps;
     std::unique_ptr<HttpCompiler> hc;
     std::unique_ptr<KafkaCompiler> kc;
+    // index[] words up to which a Kafka rule set gets its dense per-topic table (kafka_compile.h;
+    // L7G_KAFKA_DENSE_BUDGET at engine creation lowers it, for tests of the sorted-directory form)
+    size_t kafka_dense_budget = kDenseTopicBudget;
     std::unique_ptr<McCompiler> mc;
     std::unique_ptr<R2Compiler> r2;
     std::unique_ptr<CassCompiler> cs;

@@ -108,7 +108,10 @@ typedef struct {
 
 /* Engine bound to one HIP device.  err receives a message on failure.
  * device == L7G_HOST_ONLY creates a compile-only engine (policy validation and
- * rule-table statistics; classification returns hipErrorNoDevice). */
+ * rule-table statistics; classification returns hipErrorNoDevice).
+ * Environment, read here: L7G_SERVICE=0 (resident services off, below);
+ * L7G_KAFKA_DENSE_BUDGET=<u32 words> (tests: the Kafka compiler's budget for
+ * dense per-topic tables; 0 keeps every rule set to its sorted directory). */
 #define L7G_HOST_ONLY (-1)
 l7g_engine *l7g_engine_create(int device, char *err, size_t errlen);
 void l7g_engine_destroy(l7g_engine *e);
