@@ -47,6 +47,7 @@ EXPORTS = (
     "l7g_cass_session_stats",
     "l7g_classify_logged", "l7g_classify_logged_host", "l7g_kafka_api_key_name",
     "l7g_deny_replies", "l7g_deny_replies_host", "l7g_deny_reply_template",
+    "l7g_classify_logged_all", "l7g_classify_logged_all_host", "l7g_cass_action_name",
 )
 
 
@@ -69,8 +70,25 @@ class _LogKafka(C.Structure):
                 ("ntopics", C.c_uint32)]
 
 
+class _LogMcText(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("cmd_off", "cmd_len", "nkeys")]
+
+
+class _LogMcBinary(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("key_off", "key_len")]
+
+
+class _LogR2d2(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("cmd_len", "file_off", "file_len", "nfields")]
+
+
+class _LogCassandra(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("table_len", "keyword", "word_off", "word_len")]
+
+
 class _LogUnion(C.Union):
-    _fields_ = [("http", _LogHttp), ("kafka", _LogKafka)]
+    _fields_ = [("http", _LogHttp), ("kafka", _LogKafka), ("mc_text", _LogMcText), ("mc_binary", _LogMcBinary),
+                ("r2d2", _LogR2d2), ("cassandra", _LogCassandra)]
 
 
 class LogRec(C.Structure):
@@ -84,7 +102,14 @@ class LogOut(C.Structure):
     _fields_ = [("rec", C.c_void_p), ("topics", C.c_void_p), ("topic_stride", C.c_uint32)]
 
 
+class LogAllOut(C.Structure):
+    """l7g_log_all_out_t."""
+    _fields_ = [("rec", C.c_void_p), ("spans", C.c_void_p), ("span_stride", C.c_uint32),
+                ("text", C.c_void_p), ("text_stride", C.c_uint32)]
+
+
 LOG_NONE, LOG_HTTP, LOG_KAFKA = 0, 1, 2
+LOG_MC_TEXT, LOG_MC_BINARY, LOG_R2D2, LOG_CASSANDRA = 3, 4, 5, 6
 
 
 class ReplyOut(C.Structure):
@@ -173,6 +198,14 @@ def load(path=None):
                                                  C.POINTER(LogOut)]
         lib.l7g_kafka_api_key_name.restype = cp
         lib.l7g_kafka_api_key_name.argtypes = [C.c_int16]
+    # (the same for every parser's records: tests/test_generic_log_abi.py)
+    if hasattr(lib, "l7g_classify_logged_all"):
+        lib.l7g_classify_logged_all.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp, vp,
+                                                C.POINTER(LogAllOut), vp]
+        lib.l7g_classify_logged_all_host.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp,
+                                                     C.POINTER(LogAllOut)]
+        lib.l7g_cass_action_name.restype = cp
+        lib.l7g_cass_action_name.argtypes = [C.c_int16]
     # (the same for the deny replies: tests/test_deny_replies_host.py)
     if hasattr(lib, "l7g_deny_replies"):
         lib.l7g_deny_replies.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, C.POINTER(ReplyOut), vp]
@@ -203,6 +236,13 @@ def kafka_api_key_name(key):
     """The policy language's name of a Kafka API key (apiKeyToString), or None
     for a key it does not name (print that one in decimal)."""
     r = load().l7g_kafka_api_key_name(int(key))
+    return r.decode() if r is not None else None
+
+
+def cass_action_name(action):
+    """The cassandra parser's name of action id 0..37 (its queryActionMap, in
+    kernels/cass_parse.h order), or None outside."""
+    r = load().l7g_cass_action_name(int(action))
     return r.decode() if r is not None else None
 
 

@@ -8,6 +8,7 @@
 
 #include "engine/nfa_pool.h"
 #include "engine_state.h"
+#include "kernels/cass_parse.h"
 #include "policy/npds_proto.h"
 #include "regex/nfa_walk.h"
 #include "regex/re_dfa.h"
@@ -599,6 +600,19 @@ static_assert(offsetof(l7g_logrec_t, api_key) == 2 && offsetof(l7g_logrec_t, u.h
 static_assert(L7G_LOG_HTTP == LOG_HTTP && L7G_LOG_KAFKA == LOG_KAFKA, "record kinds");
 
 const char *l7g_kafka_api_key_name(int16_t key) { return KafkaApiKeyName(key); }
+
+// the members l7g_classify_logged_all adds (kernels/generic_log.hip writes words 1..4)
+static_assert(offsetof(l7g_logrec_t, u.mc_text.cmd_off) == 4 && offsetof(l7g_logrec_t, u.mc_text.nkeys) == 12 &&
+                  offsetof(l7g_logrec_t, u.mc_binary.key_off) == 4 && offsetof(l7g_logrec_t, u.mc_binary.key_len) == 8 &&
+                  offsetof(l7g_logrec_t, u.r2d2.cmd_len) == 4 && offsetof(l7g_logrec_t, u.r2d2.nfields) == 16 &&
+                  offsetof(l7g_logrec_t, u.cassandra.table_len) == 4 && offsetof(l7g_logrec_t, u.cassandra.word_len) == 16 &&
+                  offsetof(l7g_logrec_t, reserved) == 28,
+              "generic record fields");
+static_assert(L7G_LOG_MC_TEXT == LOG_MC_TEXT && L7G_LOG_MC_BINARY == LOG_MC_BINARY && L7G_LOG_R2D2 == LOG_R2D2 &&
+                  L7G_LOG_CASSANDRA == LOG_CASSANDRA,
+              "generic record kinds");
+
+const char *l7g_cass_action_name(int16_t id) { return id >= 0 && id < kCassActions ? CassActionName(id) : nullptr; }
 
 int l7g_stats(l7g_engine *e, l7g_stats_t *out) {
     std::lock_guard<std::mutex> g(e->mu);

@@ -69,13 +69,18 @@ static hipError_t GetScratch(l7g_engine *e, hipStream_t s, StreamScratch **out) 
 // log: l7g_classify_logged's outputs (device memory).  The plan is the same;
 // the Kafka grids are the logged instantiations, and http_log_kernel follows
 // the classifiers (it reads their verdicts).
+// text: l7g_classify_logged_all's (with log): the logged plan, with
+// http_log_kernel moved before the cassandra step and generic_log_kernel after
+// the cassandra classifier -- with sessions, before that call's commit.
 int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
              const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed, uint64_t *counters,
-             void *stream, const uint32_t *host_conn, const CopyIn *pre, bool *signaled, const LogOut *log) {
+             void *stream, const uint32_t *host_conn, const CopyIn *pre, bool *signaled, const LogOut *log,
+             const LogText *text) {
     std::lock_guard<std::mutex> g(e->mu);
     if (e->device < 0) return (int)hipErrorNoDevice;
     if (log && (!log->rec || ((uintptr_t)log->rec & 15) || (log->stride && !log->topics) || pre))
         return (int)hipErrorInvalidValue;
+    if (text && (!log || (text->stride && !text->text))) return (int)hipErrorInvalidValue;
     hipError_t rc = hipSetDevice(e->device);
     if (rc == hipSuccess) rc = Upload(e);
     if (rc == hipSuccess) rc = SessionsSync(e);
@@ -284,21 +289,34 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
     }
     // r2d2 (proxylib's example line protocol): one lane per request over the whole batch
     if (rc == hipSuccess && run_r2) rc = LaunchR2d2Classify(B, rt, !partitioned, big_lanes, s);
+    // every parser's access-log records: the HTTP post-pass here, where the HTTP
+    // verdicts are final, so that the generic one (which overwrites the kind 0
+    // it gives the other protocols' requests) can run before a session commit
+    if (rc == hipSuccess && text) rc = LaunchHttpLog(B, log->rec, s);
     // cassandra (proxylib): the batch's USE requests, then one lane per request
     // (with sessions on: against the session tables, then the batch's USE and PREPARE requests committed)
+    bool generic_logged = false;
     if (rc == hipSuccess && run_cs) {
         const bool sessions = e->sess.by_id != nullptr;
         const size_t need = CassandraScratchBytes(n, sessions);
         if (need == 0) rc = hipErrorInvalidValue;
         if (rc == hipSuccess) rc = S->Grow(&S->d_use, &S->use_cap, need, need);
-        if (rc == hipSuccess && sessions)
+        if (rc == hipSuccess && sessions && text) {
+            rc = LaunchCassandraSessionClassifyLogged(B, ct, e->sess, S->d_use, S->use_cap, !partitioned, big_lanes, *log,
+                                                      *text, s);
+            generic_logged = true;
+        } else if (rc == hipSuccess && sessions) {
             rc = LaunchCassandraSessionClassify(B, ct, e->sess, S->d_use, S->use_cap, !partitioned, big_lanes, s);
-        else if (rc == hipSuccess)
+        } else if (rc == hipSuccess) {
             rc = LaunchCassandraClassify(B, ct, S->d_use, S->use_cap, !partitioned, big_lanes, s);
+        }
     }
     mark(4);
     // access-log records: every request's but Kafka's (written above), from the verdicts
-    if (rc == hipSuccess && log) rc = LaunchHttpLog(B, log->rec, s);
+    if (rc == hipSuccess && log && !text) rc = LaunchHttpLog(B, log->rec, s);
+    if (rc == hipSuccess && text && !generic_logged)
+        rc = LaunchGenericLog(B, *log, *text, ct, run_cs ? CassandraSortedUseKeys(S->d_use, n) : nullptr, CassSessions{},
+                              s);
     // proxy statistics (accumulated on the device until read)
     if (rc == hipSuccess && e->flow_stats && !e->skey_list.empty()) {
         const size_t nk = e->skey_list.size();
@@ -419,6 +437,16 @@ int l7g_classify_logged(l7g_engine *e, const uint8_t *arena, uint64_t arena_len,
     const LogOut lo{reinterpret_cast<LogRec *>(log->rec), reinterpret_cast<LogSpan *>(log->topics), log->topic_stride};
     return Classify(e, arena, arena_len, off, len, conn, n, verdict, rule, consumed, counters, stream, nullptr, nullptr,
                     nullptr, &lo);
+}
+
+int l7g_classify_logged_all(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                            const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule,
+                            uint32_t *consumed, uint64_t *counters, const l7g_log_all_out_t *log, void *stream) {
+    if (!log) return (int)hipErrorInvalidValue;
+    const LogOut lo{reinterpret_cast<LogRec *>(log->rec), reinterpret_cast<LogSpan *>(log->spans), log->span_stride};
+    const LogText tx{log->text, log->text_stride};
+    return Classify(e, arena, arena_len, off, len, conn, n, verdict, rule, consumed, counters, stream, nullptr, nullptr,
+                    nullptr, &lo, &tx);
 }
 
 int l7g_frame_streams(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *s_off,

@@ -99,6 +99,17 @@ struct LogOut {
     LogSpan *topics;
     uint32_t stride;
 };
+// l7g_classify_logged_all (l7g_log_all_out_t): the records of memcached, r2d2
+// and cassandra requests as well, written by kernels/generic_log.hip; rec /
+// spans / span_stride travel as a LogOut.  Word 0 as above (api_key: the
+// binary opcode, the cassandra action id); words 1..: memcached text cmd_off,
+// cmd_len, nkeys; binary key_off, key_len; r2d2 cmd_len, file_off, file_len,
+// nfields; cassandra table_len, keyword, word_off, word_len.
+enum : uint32_t { LOG_MC_TEXT = 3, LOG_MC_BINARY = 4, LOG_R2D2 = 5, LOG_CASSANDRA = 6 };
+struct LogText {
+    uint8_t *text;  // n rows of `stride` bytes: cassandra query_table
+    uint32_t stride;
+};
 
 // A request whose bytes leave [arena, arena + arena_len) is out of contract:
 // every kernel answers it UNSUPPORTED instead of reading past the arena.

@@ -317,7 +317,7 @@ int CassReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const u
 int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
              const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed, uint64_t *counters,
              void *stream, const uint32_t *host_conn, const CopyIn *pre = nullptr, bool *signaled = nullptr,
-             const LogOut *log = nullptr);
+             const LogOut *log = nullptr, const LogText *text = nullptr);
 // classify.cc: l7g_deny_replies (device pointers; takes e->mu)
 int DenyReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
                 const uint32_t *conn, uint32_t n, const uint8_t *verdict, const l7g_reply_out_t *out, void *stream);

@@ -335,6 +335,72 @@ int l7g_classify_logged_host(l7g_engine *e, const uint8_t *arena, uint64_t arena
     return (int)rc;
 }
 
+// l7g_classify_logged_all with host buffers: l7g_classify_logged_host's
+// sequence over the same per-thread log staging, laid out [records | span rows
+// | text rows].  The caller's span and text rows go in first, so that what no
+// kernel writes (rows of other protocols, bytes past a row's written prefix)
+// comes back as it was.
+int l7g_classify_logged_all_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                                 const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict,
+                                 int32_t *rule, uint32_t *consumed, const l7g_log_all_out_t *log) {
+    if (!log || !log->rec || (log->span_stride && !log->spans) || (log->text_stride && !log->text))
+        return (int)hipErrorInvalidValue;
+    uint8_t *pa;
+    uint64_t *po;
+    uint32_t *pl, *pc;
+    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
+    if (rc0 != 0 || n == 0) return rc0;
+    memcpy(po, off, (size_t)n * 8);
+    memcpy(pl, len, (size_t)n * 4);
+    memcpy(pc, conn, (size_t)n * 4);
+    if (arena_len) memcpy(pa, arena, arena_len);
+    HostCtx *H = nullptr;
+    hipError_t rc = HostEnter(e, &H);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t rec_b = (size_t)n * sizeof(l7g_logrec_t);
+    const size_t span_b = (size_t)n * log->span_stride * sizeof(l7g_span_t);
+    const size_t text_b = (size_t)n * log->text_stride;
+    const size_t all_b = rec_b + span_b + text_b;
+    if (all_b > H->log_cap) {
+        hipStreamSynchronize(H->s);
+        if (H->log_dev) hipFree(H->log_dev);
+        if (H->log_pin) hipHostFree(H->log_pin);
+        H->log_dev = H->log_pin = nullptr;
+        H->log_cap = 0;
+        const size_t cap = all_b + all_b / 4;
+        if ((rc = hipMalloc(&H->log_dev, cap)) != hipSuccess) return (int)rc;
+        if ((rc = hipHostMalloc(&H->log_pin, cap, hipHostMallocDefault)) != hipSuccess) return (int)rc;
+        H->log_cap = cap;
+    }
+    const size_t nn = CallNn(n);
+    uint8_t *d_in = H->dev, *d_out = H->dev + H->in_cap;
+    const LogOut lo{(LogRec *)H->log_dev, span_b ? (LogSpan *)(H->log_dev + rec_b) : nullptr, log->span_stride};
+    const LogText tx{text_b ? H->log_dev + rec_b + span_b : nullptr, log->text_stride};
+    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
+    if (rc == hipSuccess && span_b + text_b) {
+        if (span_b) memcpy(H->log_pin + rec_b, log->spans, span_b);
+        if (text_b) memcpy(H->log_pin + rec_b + span_b, log->text, text_b);
+        rc = hipMemcpyAsync(H->log_dev + rec_b, H->log_pin + rec_b, span_b + text_b, hipMemcpyHostToDevice, H->s);
+    }
+    if (rc == hipSuccess)
+        rc = (hipError_t)Classify(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
+                                  (const uint32_t *)(d_in + CallLenOff(nn)), (const uint32_t *)(d_in + CallConnOff(nn)),
+                                  n, d_out, (int32_t *)(d_out + CallRuleOff(n)), (uint32_t *)(d_out + CallConsumedOff(n)),
+                                  nullptr, H->s, pc, nullptr, nullptr, &lo, &tx);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(H->pin_out, d_out, CallOutBytes(n), hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(H->log_pin, H->log_dev, all_b, hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
+    if (rc == hipSuccess) {
+        memcpy(verdict, H->pin_out, n);
+        memcpy(rule, H->pin_out + CallRuleOff(n), (size_t)n * 4);
+        memcpy(consumed, H->pin_out + CallConsumedOff(n), (size_t)n * 4);
+        memcpy(log->rec, H->log_pin, rec_b);
+        if (span_b) memcpy(log->spans, H->log_pin + rec_b, span_b);
+        if (text_b) memcpy(log->text, H->log_pin + rec_b + span_b, text_b);
+    }
+    return (int)rc;
+}
+
 // l7g_deny_replies with host buffers, over the calling thread's stream and
 // staging: the inputs and the verdicts copied in, the reply kernels, the
 // sizes copied out and waited for, then the bytes that were written.  The

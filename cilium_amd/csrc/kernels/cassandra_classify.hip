@@ -406,9 +406,10 @@ hipError_t LaunchCassandraClassify(const Batch &B, const CassTables &T, void *sc
 // of the batch's PREPAREs and keyspaces (separate launches: the kernel
 // boundaries order the tables' readers and writers).
 // scratch: CassandraScratchBytes(B.n, true) bytes
-hipError_t LaunchCassandraSessionClassify(const Batch &B, const CassTables &T, const CassSessions &SS, void *scratch,
-                                          size_t scratch_bytes, bool answer_other, uint32_t nfa_lanes,
-                                          hipStream_t stream) {
+// commit: false leaves the commit launches to the caller (the logged sequence below)
+static hipError_t SessionClassify(const Batch &B, const CassTables &T, const CassSessions &SS, void *scratch,
+                                  size_t scratch_bytes, bool answer_other, uint32_t nfa_lanes, hipStream_t stream,
+                                  bool commit) {
     if (B.n == 0) return hipSuccess;
     const size_t kb = KeyBytes(B.n);
     uint8_t *base = (uint8_t *)scratch;
@@ -430,8 +431,37 @@ hipError_t LaunchCassandraSessionClassify(const Batch &B, const CassTables &T, c
     hipLaunchKernelGGL(cassandra_session_classify_kernel, cgrid, dim3(kBlock), 0, stream, B, T, sorted,
                        answer_other ? 1u : 0u, SS);
     rc = hipGetLastError();
+    if (rc != hipSuccess || !commit) return rc;
+    return LaunchCassandraCommit(B, T, SS, sorted, psorted, stream);
+}
+
+hipError_t LaunchCassandraSessionClassify(const Batch &B, const CassTables &T, const CassSessions &SS, void *scratch,
+                                          size_t scratch_bytes, bool answer_other, uint32_t nfa_lanes,
+                                          hipStream_t stream) {
+    return SessionClassify(B, T, SS, scratch, scratch_bytes, answer_other, nfa_lanes, stream, true);
+}
+
+// l7g_classify_logged_all's sequence: the same launches, with the access-log
+// post-pass between the read-only classifier and the commit, where the session
+// tables still stand as the classifier read them.
+hipError_t LaunchCassandraSessionClassifyLogged(const Batch &B, const CassTables &T, const CassSessions &SS,
+                                                void *scratch, size_t scratch_bytes, bool answer_other,
+                                                uint32_t nfa_lanes, const LogOut &L, const LogText &X,
+                                                hipStream_t stream) {
+    if (B.n == 0) return hipSuccess;
+    hipError_t rc = SessionClassify(B, T, SS, scratch, scratch_bytes, answer_other, nfa_lanes, stream, false);
+    if (rc != hipSuccess) return rc;
+    const size_t kb = KeyBytes(B.n);
+    const uint64_t *sorted = (const uint64_t *)((uint8_t *)scratch + kb);
+    const uint64_t *psorted = (const uint64_t *)((uint8_t *)scratch + 3 * kb);
+    rc = LaunchGenericLog(B, L, X, T, sorted, SS, stream);
     if (rc != hipSuccess) return rc;
     return LaunchCassandraCommit(B, T, SS, sorted, psorted, stream);
+}
+
+// The sorted USE keys the launchers above left in `scratch` for a batch of n requests.
+const uint64_t *CassandraSortedUseKeys(const void *scratch, uint32_t n) {
+    return (const uint64_t *)((const uint8_t *)scratch + KeyBytes(n));
 }
 
 }  // namespace l7

@@ -42,6 +42,16 @@ hipError_t LaunchCassandraClassify(const Batch &B, const CassTables &T, void *sc
 hipError_t LaunchCassandraSessionClassify(const Batch &B, const CassTables &T, const CassSessions &SS, void *scratch,
                                           size_t scratch_bytes, bool answer_other, uint32_t nfa_lanes,
                                           hipStream_t stream);
+// l7g_classify_logged_all (kernels/generic_log.hip): the records of memcached, r2d2 and cassandra requests,
+// after LaunchHttpLog; use_keys: CassandraSortedUseKeys of this call's cassandra scratch (null: no cassandra
+// classifier ran); with sessions the launch is made by LaunchCassandraSessionClassifyLogged, before the commit
+hipError_t LaunchGenericLog(const Batch &B, const LogOut &L, const LogText &X, const CassTables &T,
+                            const uint64_t *use_keys, const CassSessions &SS, hipStream_t stream);
+hipError_t LaunchCassandraSessionClassifyLogged(const Batch &B, const CassTables &T, const CassSessions &SS,
+                                                void *scratch, size_t scratch_bytes, bool answer_other,
+                                                uint32_t nfa_lanes, const LogOut &L, const LogText &X,
+                                                hipStream_t stream);
+const uint64_t *CassandraSortedUseKeys(const void *scratch, uint32_t n);
 hipError_t LaunchCassandraCommit(const Batch &B, const CassTables &T, const CassSessions &S,
                                  const uint64_t *use_sorted, const uint64_t *prep_sorted, hipStream_t stream);
 hipError_t LaunchCassandraReplies(const Batch &B, const CassSessions &S, void *scratch, size_t scratch_bytes,

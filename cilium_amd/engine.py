@@ -187,6 +187,58 @@ class Engine:
             raise RuntimeError(f"l7g_classify_logged_host failed: HIP error {rc}")
         return v, r, c, rec, topics
 
+    def classify_logged_all_device(self, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, verdict_ptr, rule_ptr,
+                                   consumed_ptr, records_ptr, spans_ptr=0, span_stride=0, text_ptr=0, text_stride=0,
+                                   counters_ptr=0, stream=0):
+        """l7g_classify_logged_all: classify_logged_device, with the records of
+        memcached, r2d2 and cassandra requests as well; spans_ptr: n rows of
+        span_stride 8-byte spans (Kafka topics, memcached text keys), text_ptr:
+        n rows of text_stride bytes (cassandra query_table).  All pointers are
+        device addresses."""
+        lo = _lib.LogAllOut(records_ptr, spans_ptr or None, span_stride, text_ptr or None, text_stride)
+        rc = self._lib.l7g_classify_logged_all(self._h, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n,
+                                               verdict_ptr, rule_ptr, consumed_ptr, counters_ptr or None, C.byref(lo),
+                                               stream or None)
+        if rc != 0:
+            raise RuntimeError(f"l7g_classify_logged_all failed: HIP error {rc}")
+
+    def classify_logged_all(self, arena, offsets, lengths, conn_ids, span_stride=4, text_stride=64, spans=None,
+                            text=None):
+        """classify_logged(), for every parser: returns (verdict, rule,
+        consumed, records, spans, text).  records is a LOGREC_DTYPE array: read
+        the mc_* fields where kind == 3, mcb_* where 4, r2_* where 5, cass_*
+        where 6 (and http_* / kafka_* as before), only where the verdict is
+        ALLOW or DENY.  spans is an (n, span_stride) SPAN_DTYPE array (Kafka
+        topics, memcached text keys), text an (n, text_stride) uint8 array
+        (cassandra query_table); what no kernel writes keeps what `spans` /
+        `text` held (zeros when not given).  log_entries() turns the outputs
+        into the reference's log entries."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        n = len(off)
+        v = np.zeros(n, np.uint8)
+        r = np.zeros(n, np.int32)
+        c = np.zeros(n, np.uint32)
+        rec = np.zeros(n, LOGREC_DTYPE)
+        if spans is None:
+            spans = np.zeros((n, span_stride), SPAN_DTYPE)
+        spans = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+        if text is None:
+            text = np.zeros((n, text_stride), np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        if spans.shape != (n, span_stride) or text.shape != (n, text_stride):
+            raise ValueError("spans must have shape (n, span_stride) and text (n, text_stride)")
+        lo = _lib.LogAllOut(rec.ctypes.data, spans.ctypes.data if span_stride else None, span_stride,
+                            text.ctypes.data if text_stride else None, text_stride)
+        rc = self._lib.l7g_classify_logged_all_host(self._h, arena.ctypes.data, arena.nbytes, off.ctypes.data,
+                                                    ln.ctypes.data, cid.ctypes.data, n, v.ctypes.data, r.ctypes.data,
+                                                    c.ctypes.data, C.byref(lo))
+        if rc != 0:
+            raise RuntimeError(f"l7g_classify_logged_all_host failed: HIP error {rc}")
+        return v, r, c, rec, spans, text
+
     # ---------------------------------------------------------- deny replies
     def deny_replies_device(self, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, verdict_ptr, buf_ptr, cap,
                             reply_off_ptr, reply_len_ptr, total_ptr, stream=0):
@@ -371,14 +423,81 @@ assert CONN_DTYPE.itemsize == C.sizeof(Conn)
 
 
 # l7g_logrec_t as a numpy record: the union's two views over the same bytes
+# (mc_*: u.mc_text, mcb_*: u.mc_binary, r2_*: u.r2d2, cass_*: u.cassandra -- l7g_classify_logged_all's)
+_LOGREC_GENERIC = [("mc_cmd_off", 4), ("mc_cmd_len", 8), ("mc_nkeys", 12), ("mcb_key_off", 4), ("mcb_key_len", 8),
+                   ("r2_cmd_len", 4), ("r2_file_off", 8), ("r2_file_len", 12), ("r2_nfields", 16),
+                   ("cass_table_len", 4), ("cass_keyword", 8), ("cass_word_off", 12), ("cass_word_len", 16)]
 LOGREC_DTYPE = np.dtype({
     "names": ["kind", "flags", "api_key", "method_len", "path_len", "host_off", "host_len", "head_len", "nheaders",
-              "api_version", "correlation_id", "ntopics"],
-    "formats": ["u1", "u1", "<i2", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<i2", "<i4", "<u4"],
-    "offsets": [0, 1, 2, 4, 8, 12, 16, 20, 24, 4, 8, 12],
+              "api_version", "correlation_id", "ntopics"] + [k for k, _ in _LOGREC_GENERIC],
+    "formats": ["u1", "u1", "<i2", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<i2", "<i4", "<u4"] +
+               ["<u4"] * len(_LOGREC_GENERIC),
+    "offsets": [0, 1, 2, 4, 8, 12, 16, 20, 24, 4, 8, 12] + [o for _, o in _LOGREC_GENERIC],
     "itemsize": 32})
 SPAN_DTYPE = np.dtype([("off", "<u4"), ("len", "<u4")])
 assert LOGREC_DTYPE.itemsize == C.sizeof(_lib.LogRec) and SPAN_DTYPE.itemsize == C.sizeof(_lib.Span)
+
+
+CASS_KEYWORDS = ("alter", "create", "drop", "truncate", "list")  # l7g_logrec_t u.cassandra.keyword
+
+
+def log_entries(verdict, records, spans, text, arena, offsets, lengths):
+    """The LogEntry_GenericL7 entries of a classify_logged_all() batch as the
+    proxylib parsers log them: a list with, per request, None (no entry: a
+    verdict other than ALLOW / DENY, an HTTP or Kafka request, a cassandra
+    request whose path has no four parts) or (entry_type, proto, fields) with
+    entry_type "Request" (ALLOW) or "Denied" (DENY), proto the parser's name
+    and fields a dict of bytes values (Go strings are bytes).  A request whose
+    span or text row was too short for it (flags bit0), or a cassandra EXECUTE
+    whose stored action has no name (flags bit2), raises ValueError."""
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    out = []
+    for i in range(len(records)):
+        r = records[i]
+        kind, v = int(r["kind"]), int(verdict[i])
+        if v not in (_lib.ALLOW, _lib.DENY) or kind < _lib.LOG_MC_TEXT:
+            out.append(None)
+            continue
+        et = "Request" if v == _lib.ALLOW else "Denied"
+        req = arena[int(offsets[i]):int(offsets[i]) + int(lengths[i])].tobytes()
+        flags = int(r["flags"])
+
+        def cut(o, n):
+            return req[int(o):int(o) + int(n)]
+        if kind == _lib.LOG_MC_TEXT:
+            if flags & 1:
+                raise ValueError(f"request {i}: {int(r['mc_nkeys'])} keys, more than the span stride")
+            keys = [cut(s["off"], s["len"]) for s in spans[i][:int(r["mc_nkeys"])]]
+            out.append((et, "textmemcached", {"command": cut(r["mc_cmd_off"], r["mc_cmd_len"]),
+                                              "keys": b", ".join(keys)}))
+        elif kind == _lib.LOG_MC_BINARY:
+            out.append((et, "binarymemcached", {"opcode": str(int(r["api_key"])).encode(),
+                                                "key": cut(r["mcb_key_off"], r["mcb_key_len"])}))
+        elif kind == _lib.LOG_R2D2:
+            out.append((et, "r2d2", {"cmd": cut(0, r["r2_cmd_len"]), "file": cut(r["r2_file_off"], r["r2_file_len"])}))
+        elif kind == _lib.LOG_CASSANDRA:
+            if not flags & 2:
+                out.append(None)
+                continue
+            if flags & 1:
+                raise ValueError(f"request {i}: a table of {int(r['cass_table_len'])} bytes, more than the text stride")
+            if flags & 4:
+                raise ValueError(f"request {i}: the stored statement's action has no name")
+            a = int(r["api_key"])
+            if a >= 0:
+                action = _lib.cass_action_name(a).encode()
+            else:
+                # (Go lowers the whole query first; ASCII-only lowering here is exact for ASCII words)
+                word = cut(r["cass_word_off"], r["cass_word_len"]).decode("utf-8", "surrogateescape").lower() \
+                    .encode("utf-8", "surrogateescape")
+                action = CASS_KEYWORDS[int(r["cass_keyword"])].encode() + b"-" + word
+                if word == b"materialized":
+                    action += b"-view"
+            out.append((et, "cassandra", {"query_action": action,
+                                          "query_table": text[i][:int(r["cass_table_len"])].tobytes()}))
+        else:
+            out.append(None)
+    return out
 
 
 def conns_array(conns):

@@ -273,6 +273,11 @@ typedef struct {
     union {
         struct { uint32_t method_len, path_len, host_off, host_len, head_len, nheaders; } http;
         struct { int16_t api_version, pad; int32_t correlation_id; uint32_t ntopics; } kafka;
+        /* l7g_classify_logged_all only (below) */
+        struct { uint32_t cmd_off, cmd_len, nkeys; } mc_text;
+        struct { uint32_t key_off, key_len; } mc_binary;
+        struct { uint32_t cmd_len, file_off, file_len, nfields; } r2d2;
+        struct { uint32_t table_len, keyword, word_off, word_len; } cassandra;
     } u;
     uint32_t reserved; /* 0 */
 } l7g_logrec_t; /* 32 bytes */
@@ -286,6 +291,81 @@ int l7g_classify_logged_host(l7g_engine *e, const uint8_t *arena, uint64_t arena
 /* The API key's name as the policy language spells it (apiKeyToString,
  * pkg/proxy/kafka.go:162-167); NULL = unknown: print the key in decimal. */
 const char *l7g_kafka_api_key_name(int16_t key);
+
+/* Access-log records of every parser (opt-in; none of the calls above is
+ * touched by it).  l7g_classify_logged_all is l7g_classify_logged -- the same
+ * verdict / rule / consumed / counters, and for HTTP and Kafka requests byte
+ * for byte the same record and row, spans / span_stride standing for topics /
+ * topic_stride -- and also writes the fields of the one
+ * LogEntry_GenericL7 { Proto, Fields } the proxylib parsers log per request on
+ * memcached, r2d2 and cassandra connections.  As before a record means
+ * something only where the verdict is L7G_ALLOW (entry type Request) or
+ * L7G_DENY (Denied).  All offsets are from the request's first byte.
+ *
+ * memcached text (kind 3, Proto "textmemcached", text/parser.go:98-171):
+ *   "command" is request bytes [cmd_off, cmd_off + cmd_len) -- tokens[0] of
+ *   bytes.Fields(first line), which need not start at byte 0 -- and "keys" the
+ *   nkeys key tokens joined by ", ": tokens[1:] for get*, tokens[2:] for gat*,
+ *   tokens[1:2] for storage commands, delete, incr, decr and touch, none for
+ *   every other command.  Row i of spans receives the first
+ *   min(nkeys, span_stride) key spans; flags bit0 = nkeys > span_stride
+ *   (submit the request again with a stride of its nkeys).
+ * memcached binary (kind 4, "binarymemcached", binary/parser.go:97-105):
+ *   "opcode" is api_key in decimal (request byte 1), "key" request bytes
+ *   [key_off, key_off + key_len) with key_off = 24 + the extras length; a key
+ *   length of 0 gives key_off 0.  Which of the two parsers a connection has is
+ *   the classifier's choice (the connection's L7G_CONN_MC_* flags, else the
+ *   request's first byte).
+ * r2d2 (kind 5, "r2d2", r2d2parser.go:175-205): "cmd" is request bytes
+ *   [0, cmd_len); nfields the length of strings.Split(line, " ") (empty fields
+ *   count); "file" is [file_off, file_off + file_len) -- field 1 -- when
+ *   nfields is 2, else empty (file_off and file_len 0).
+ * cassandra (kind 6, "cassandra", cassandraparser.go:223-244): flags bit1 is
+ *   set iff the reference logs an entry for the request: its path has exactly
+ *   four '/'-separated parts, that is a QUERY or PREPARE (with sessions also a
+ *   resolved EXECUTE) whose action and table hold no '/'.  Every other opcode
+ *   has a two-part path and logs nothing.  "query_table" is the table as a
+ *   rule's regex sees it (lowered; an undotted table of an action other than
+ *   use prefixed with the keyspace and '.'), table_len bytes, of which the
+ *   first min(table_len, text_stride) are written to row i of text; flags bit0
+ *   = table_len > text_stride.  An empty table is logged as "".
+ *   "query_action" is l7g_cass_action_name(api_key) for api_key 0..37.
+ *   api_key -1 is an action outside the parser's queryActionMap, built by the
+ *   caller as lower(kw) + "-" + lower(word) (+ "-view" when word lowers to
+ *   "materialized"): kw is keyword (0 alter, 1 create, 2 drop, 3 truncate,
+ *   4 list) and word the request bytes [word_off, word_off + word_len), the
+ *   query's second field.  A resolved EXECUTE takes the action and table of
+ *   its stored statement; limits of what a statement stores: for a stored
+ *   action of -1 the word is gone (flags bit2: the action name is
+ *   unavailable), and a stored table is kept only up to its first '/', so an
+ *   EXECUTE of such a statement is logged with the cut table where the
+ *   reference logs nothing.
+ *   The keyspace is that of the last USE before the request on its connection
+ *   in the batch; with sessions on, before the batch's first USE, the stored
+ *   one, and statements resolve as they stood before the call.
+ *
+ * Rows of spans are written for Kafka and memcached text requests only, rows
+ * of text for cassandra requests only, and never past the prefix named above.
+ * spans NULL with span_stride 0 and text NULL with text_stride 0 are valid
+ * (no rows are written); a non-zero stride with a NULL pointer is
+ * hipErrorInvalidValue, a host-only engine answers hipErrorNoDevice.  rec,
+ * spans and text are device memory for l7g_classify_logged_all (rec 16-byte
+ * aligned) and host memory for l7g_classify_logged_all_host, which always
+ * launches. */
+enum { L7G_LOG_MC_TEXT = 3, L7G_LOG_MC_BINARY = 4, L7G_LOG_R2D2 = 5, L7G_LOG_CASSANDRA = 6 };
+typedef struct {
+    l7g_logrec_t *rec;                          /* n records, 16-byte aligned */
+    l7g_span_t *spans; uint32_t span_stride;    /* n rows: Kafka topics, memcached text keys */
+    uint8_t *text;     uint32_t text_stride;    /* n rows of bytes: cassandra query_table */
+} l7g_log_all_out_t;
+int l7g_classify_logged_all(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                            const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule,
+                            uint32_t *consumed, uint64_t *counters, const l7g_log_all_out_t *log, void *stream);
+int l7g_classify_logged_all_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                                 const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict,
+                                 int32_t *rule, uint32_t *consumed, const l7g_log_all_out_t *log);
+/* CassActionName: the parser's name of action id 0..37; NULL outside. */
+const char *l7g_cass_action_name(int16_t id);
 
 /* Deny replies (opt-in; l7g_classify and everything it launches are untouched
  * by it).  A post-pass over a classified batch: for every request whose
