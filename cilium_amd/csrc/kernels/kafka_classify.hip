@@ -59,19 +59,38 @@ __device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_amdgcn_
 struct GRd {
     static constexpr bool kWin = true;
     const uint8_t *b;
-    uintptr_t lastc;  // the last 16-byte chunk holding a request byte (window loads never pass it)
+    uint32_t end;     // the request's length: the call's until the frame's is known, then that (every read
+                      // lies inside the frame).  lastr(), the last 16-byte chunk holding a byte of it (window
+                      // and block loads never pass it), as a ksched position (rel), is formed from it where
+                      // it is used: the walk holds the length anyway, and a chunk address was two registers
+    __device__ __forceinline__ uint32_t lastr() const {
+        uint32_t e = end;
+        asm volatile("" : "+v"(e));
+        return (rel(e) - 1) & ~15u;
+    }
     Cur cur;
     uint8_t *stage;   // the lane's CRC staging slot (win9 stages the message window there)
-    uint32_t hlim;    // while the slot holds the request's first four chunks (stage_head): the
-                      // request bytes [0, hlim) it holds, else 0
+    uint32_t span;    // the span the slot holds: the 64 bytes from request byte span (modulo 2^32: the
+                      // head's lies up to 15 bytes before byte 0), a 16-byte aligned address, or
+                      // ksched::kNoSpan.  (ksched, kafka_sched.h, counts positions from the 16-byte aligned
+                      // address at or below b: rel(pos).)  stage_head, win9 and the
+                      // window-path CRC set it; the exact-path CRC takes the slot without saying what
+                      // it leaves.  Chunks past lastr() hold that chunk's bytes, not their own: every field
+                      // read here ends at or below the request's last byte (kd_read bounds it, a
+                      // string's last word is masked), so it lies in chunks that hold their own.
+    __device__ __forceinline__ const uint8_t *base() const {
+        return reinterpret_cast<const uint8_t *>((uintptr_t)b & ~(uintptr_t)15);
+    }
+    __device__ __forceinline__ uintptr_t lastc() const { return (uintptr_t)base() + lastr(); }
+    __device__ __forceinline__ uint32_t rel(uint32_t pos) const { return pos + (uint32_t)((uintptr_t)b & 15); }
     // The request's first 64 bytes (size, kind, version, client id, and for a
     // produce its acks, timeout, first topic and partition) staged into the
     // slot in one round trip; the fields there are read from LDS until win9 or
     // a CRC takes the slot over, where the cursor took a round trip per chunk
     // (cfg5 Kafka 15.54 -> 15.26 ms)
     __device__ __forceinline__ void stage_head() {
-        crc_stage(stage, reinterpret_cast<const uint8_t *>((uintptr_t)b & ~(uintptr_t)15), lastc);
-        hlim = 64 - (uint32_t)((uintptr_t)b & 15);
+        crc_stage_at(stage, base(), 0, lastr());
+        span = 0u - rel(0);
     }
     // little-endian 4 bytes at byte rel (rel + 4 <= 64) of the staged chunks
     __device__ __forceinline__ uint32_t slot_le4(uint32_t rel) {
@@ -87,39 +106,55 @@ struct GRd {
                      : "memory");
         return __builtin_amdgcn_alignbyte(hi, lo, rel & 3);
     }
+    // A field whose four bytes lie in the span comes from the slot, any other
+    // through the cursor (which a slot read leaves as it is): after a message
+    // set the slot holds the block its last message ended in, so the partition
+    // or topic header behind the set is read without a round trip as far as
+    // that block reaches.
     __device__ __forceinline__ uint32_t le4(uint32_t pos) {
-        if (pos + 4 <= hlim) return slot_le4(pos + (uint32_t)((uintptr_t)b & 15));
+        const uint32_t o = pos - span;
+        if (o <= 60u) return slot_le4(o);
         return le_load4(cur, b + pos);
     }
     __device__ __forceinline__ uint64_t be(uint32_t pos, int n) {
-        if (n <= 4 && pos + 4 <= hlim) {
-            const uint32_t v = bswap(slot_le4(pos + (uint32_t)((uintptr_t)b & 15)));
+        const uint32_t o = pos - span;
+        if (n <= 4 && o <= 60u) {
+            const uint32_t v = bswap(slot_le4(o));
             return n == 4 ? v : v >> (32 - 8 * n);
         }
         return be_load(cur, b + pos, n);
     }
-    // bytes [pos, pos + 36) as little-endian words: the four chunks that can
-    // hold them staged together into the lane's CRC slot (one memory round
-    // trip), chunks past the request's last one clamped to it (their bytes are
-    // never used), and read back.  The cursor is left on the chunk of byte
-    // pos + 16, where the message's CRC input starts, and the slot keeps the
-    // window for the CRC (crc32_ieee_window: its first 32-48 bytes cost no
-    // further round trip; cfg5 Kafka 16.06 -> 15.53 ms)
+    // bytes [pos, pos + 36) as little-endian words.  When the span holds them
+    // (the block the message before ended in, which the CRC left in the slot)
+    // they are cut from it as they lie; else the four chunks that can hold them
+    // are staged together into the slot (one memory round trip), chunks past the
+    // request's last one clamped to it (their bytes are never used), and read
+    // back.  The cursor is left on the chunk of byte pos + 16, where the
+    // message's CRC input starts, and the slot keeps the window block for the
+    // CRC (crc32_ieee_window: its bytes there cost no further round trip; cfg5
+    // Kafka 16.06 -> 15.53 ms)
     __device__ __forceinline__ void win9(uint32_t pos, uint32_t (&x)[9]) {
         const uintptr_t a = (uintptr_t)(b + pos);
         const uintptr_t c0 = a & ~(uintptr_t)15;
         uint32_t w[16];
         {
-            hlim = 0;  // the head leaves the slot
-            crc_stage(stage, reinterpret_cast<const uint8_t *>(c0), lastc);
-            const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * lane_id());
+            const uint32_t s = rel(pos);
+            const uint32_t wb = ksched::window_base(span + rel(0), s);
+            if (wb - rel(0) != span) {
+                span = wb - rel(0);
+                crc_stage_at(stage, base(), wb, lastr());
+            }
+            // the window's first chunk is the slot's first or (s - wb >= 16, at most 28) its second,
+            // and then its last word lies in the slot's fourth chunk, which is read as that
+            const uint32_t la3 = (uint32_t)(uintptr_t)(stage + 16 * lane_id()) + 3072;
+            const uint32_t la = la3 - 3072 + (((s - wb) >> 4) << 10);
             uint4 v0, v1, v2, v3;
             asm volatile("s_waitcnt vmcnt(0)\n\t"
                          "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\t"
-                         "ds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072\n\t"
+                         "ds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %5\n\t"
                          "s_waitcnt lgkmcnt(0)"
                          : "=v"(v0), "=v"(v1), "=v"(v2), "=v"(v3)
-                         : "v"(la)
+                         : "v"(la), "v"(la3)
                          : "memory");
             const uint4 vv[4] = {v0, v1, v2, v3};
 #pragma unroll
@@ -135,12 +170,12 @@ struct GRd {
             x[i] = __builtin_amdgcn_alignbyte(hi, lo, s & 3);
         }
         // byte pos + 16 is in chunk 1 (s < 16): hand it to the cursor
-        cur.line = c0 + 16 <= lastc ? c0 + 16 : ~(uintptr_t)0;
+        cur.line = (rel(pos) & ~15u) + 16 <= lastr() ? c0 + 16 : ~(uintptr_t)0;
         cur.w0 = w[4]; cur.w1 = w[5]; cur.w2 = w[6]; cur.w3 = w[7];
     }
-    // big-endian 4 bytes at byte rel (rel + 4 <= 64) of the window win9 left in
-    // the slot: a field past the 36 bytes win9 returns, without a round trip
-    __device__ __forceinline__ uint32_t win_be4(uint32_t rel) { return bswap(slot_le4(rel)); }
+    // big-endian 4 bytes at byte o (o + 4 <= 64) of the slot, which holds the window block win9 left
+    // there: a field past the 36 bytes win9 returns, without a round trip
+    __device__ __forceinline__ uint32_t win_be4(uint32_t o) { return bswap(slot_le4(o)); }
 };
 
 // ---------------- io.ReadFull / LimitReader decoding over a byte source ----------------
@@ -260,9 +295,9 @@ __device__ __forceinline__ int kd_message_set(R &r, uint32_t &pos, uint32_t end,
                 // from the window in the slot when it holds the field (short
                 // keys), else through the cursor, kept on byte at + 4's chunk
                 // where the CRC starts (crc_head hashes it without a round trip)
-                const uint32_t rel = vo - dec.pos + (uint32_t)((uintptr_t)(r.b + dec.pos) & 15);
-                if (rel + 4 <= 64) {
-                    vlen = (int32_t)r.win_be4(rel);
+                const uint32_t o = vo - r.span;
+                if (o <= 60u) {
+                    vlen = (int32_t)r.win_be4(o);
                 } else {
                     const Cur keep = r.cur;
                     vlen = (int32_t)r.be(vo, 4);
@@ -340,13 +375,14 @@ __device__ __forceinline__ int kafka_walk(R &r, uint32_t rawlen, int kind, bool 
         kd_skip(d, 2); kd_skip(d, 4);
         nt = kd_arraylen(d, false, bad);
         if (bad) { rc = -1; break; }
-        for (int32_t t = 0; t < nt && rc == 0; t++) {
+        // (both loops count down: the count and the index were two registers each across the sets' CRCs)
+        for (; nt > 0 && rc == 0; nt--) {
             kd_string(d, o, l);
             if (d.err) break;
             h.topic(o, l);
             np = kd_arraylen(d, false, bad);
             if (bad) { rc = -1; break; }
-            for (int32_t p = 0; p < np; p++) {
+            for (; np > 0; np--) {
                 kd_skip(d, 4);
                 if (d.err) { rc = -1; break; }
                 const int32_t ss = (int32_t)kd_int(d, 4);
@@ -572,13 +608,19 @@ struct TopicLog {
 template <class L>
 struct ExactHooks {
     const KafkaTables &T;
-    const DevKafkaRuleset &rs;
+    int32_t rsi;  // the connection's rule set, T.rulesets[rsi]: its address is formed at each use (the index is
+                  // one register across the walk, the address two)
     ReqInfo &q;
     GRd &r;
     const uint32_t *crctab;
     uint8_t *stage;
     uint32_t ntopics, cmax;
     L log;
+    __device__ __forceinline__ const DevKafkaRuleset &rs() const {
+        int32_t k = rsi;
+        asm volatile("" : "+v"(k));
+        return T.rulesets[k];
+    }
     __device__ __forceinline__ void client(uint32_t o, uint32_t l) {
         q.client = str_lookup(T.client_hash, T.client_mask, T.strings, r, o, l);
         if (q.client < 0) q.client = -2;
@@ -591,17 +633,20 @@ struct ExactHooks {
         }
         ntopics++;
         const int32_t tid = l > 0 ? str_lookup(T.topic_hash, T.topic_mask, T.strings, r, o, l) : -1;
-        const uint32_t e = topic_first(T, rs, q, tid);
+        const uint32_t e = topic_first(T, rs(), q, tid);
         cmax = cmax > e ? cmax : e;
     }
     // CRC32-IEEE of the message bytes [pos, pos + n) against the stored value
     __device__ __forceinline__ bool msg(uint32_t pos, uint32_t n, uint32_t stored) {
-        r.hlim = 0;  // the CRC takes the slot over
-        return crc32_ieee_staged(crctab, r.cur, r.b + pos, n, stage, r.lastc) == stored;
+        r.span = ksched::kNoSpan;  // the CRC takes the slot over
+        return crc32_ieee_staged(crctab, r.cur, r.b + pos, n, stage, r.lastc()) == stored;
     }
     // the same, right after the walk's window read of this message (kd_message_set's fast path)
+    // (whatever the answer, the slot then holds the block the message ended in, or still its window block)
     __device__ __forceinline__ bool msg_win(uint32_t pos, uint32_t n, uint32_t stored) {
-        return crc32_ieee_window(crctab, r.cur, r.b + pos, n, stage, r.lastc) == stored;
+        const uint32_t p = r.rel(pos), wb = r.rel(r.span);
+        r.span = ksched::keep_base(wb, p + n) - r.rel(0);
+        return crc32_ieee_window(crctab, r.cur, r.b, wb, p, p + n, stage, r.lastr()) == stored;
     }
 };
 
@@ -696,7 +741,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
             if (verdict == V_UNSUPPORTED) break;
             if (!l7_in_arena(off, len, B.arena_len)) { verdict = V_UNSUPPORTED; break; }  // out of contract
             if (len < 4) { verdict = V_INCOMPLETE; break; }
-            GRd r{B.arena + off, ((uintptr_t)(B.arena + off) + len - 1) & ~(uintptr_t)15, {}, stage, 0};
+            GRd r{B.arena + off, len, {}, stage, ksched::kNoSpan};
             r.stage_head();
             r.cur.line = ~(uintptr_t)0;
             const int32_t size = (int32_t)r.be(0, 4);
@@ -705,16 +750,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
             if ((uint64_t)(uint32_t)size + 4 > kMaxParseBuf) break;
             const uint32_t rawlen = (uint32_t)size + 4;
             if (rawlen > len) { verdict = V_INCOMPLETE; break; }
+            r.end = rawlen;
             if (rawlen < 12) break;
             ReqInfo q;
             q.kv = (uint32_t)r.be(4, 4);  // (rawlen >= 12: both fields)
             q.client = -2;
             // fields are read where they are used: a copy would hold 9 VGPRs across the decode
-            const DevKafkaRuleset &rs = T.rulesets[conn.ruleset];
             using Log = typename std::conditional<kLog, TopicLog, NoTopicLog>::type;
             Log lg{};
             if constexpr (kLog) lg = TopicLog{ltopics + (size_t)idx * lstride, lstride};
-            ExactHooks<Log> h{T, rs, q, r, crctab, stage, 0, 0, lg};
+            ExactHooks<Log> h{T, conn.ruleset, q, r, crctab, stage, 0, 0, lg};
             if (q.typed_() && kafka_walk(r, rawlen, q.kind_(), zflag, h) == -1) break;
             consumed = rawlen;
             verdict = V_DENY;
@@ -726,6 +771,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
                                   q.kv & 0xFFFFu, corr, h.ntopics);
                 o[1] = make_uint4(0, 0, 0, 0);
             }
+            const DevKafkaRuleset &rs = h.rs();
             if (!rs.any) break;
             const uint32_t best = matches_rule(T, rs, q, h.ntopics, h.cmax);
             if (best != kInf) { verdict = V_ALLOW; rule = T.rules[rs.rule_first + best].gid; }

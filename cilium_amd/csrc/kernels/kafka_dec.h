@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "gmem.h"
+#include "kafka_sched.h"
 
 namespace l7 {
 namespace {
@@ -269,8 +270,8 @@ __device__ __forceinline__ uint32_t cur_word_at(const Cur &c, uint32_t k) {
 // bytes, and a batch is waited for with vmcnt(0).  The last, short batch is
 // staged too (crc_last): its up to four chunks cost one round trip, where the
 // cursor took one per chunk (cfg5 Kafka 16.45 -> 16.10 ms).  A message the walk
-// reads through its window starts from the window already in the slot
-// (crc32_ieee_window).
+// reads through its window starts from the window already in the slot and
+// leaves its last block there for the walk (crc32_ieee_window).
 
 // bytes before the first 16-byte boundary (at most 15, one chunk) in 8-, 4-
 // and 1-byte steps; returns how many were hashed into c
@@ -308,9 +309,23 @@ __device__ __forceinline__ void crc_stage(uint8_t *stage, const uint8_t *q, uint
                                          (__attribute__((address_space(3))) void *)(stage + k * 1024), 16, 0, 0);
     }
 }
-// one staged 64-byte batch hashed into c; the next one (if any) staged meanwhile
-__device__ __forceinline__ uint32_t crc_batch(const uint32_t *tab, uint8_t *stage, uint32_t c, const uint8_t *next,
-                                              uintptr_t lastc) {
+// The same with positions for addresses (ksched, kafka_sched.h): position y is the byte at
+// o + (y - (o & 15)), o the request's first byte (or the aligned address at or below it) and y at or
+// after it; lastr is the request's last chunk.  The walk holds lastr in one register and o anyway, where
+// a chunk address is two.
+__device__ __forceinline__ void crc_stage_at(uint8_t *stage, const uint8_t *o, uint32_t x, uint32_t lastr) {
+    const uint32_t k0 = (uint32_t)((uintptr_t)o & 15);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t y = x + 16 * k <= lastr ? x + 16 * k : lastr;
+        __builtin_amdgcn_global_load_lds((const void *)(o + (y - k0)),
+                                         (__attribute__((address_space(3))) void *)(stage + k * 1024), 16, 0, 0);
+    }
+}
+// one staged 64-byte batch hashed into c; stage_next() is called once the batch is in registers and stages the
+// next one, if any, meanwhile
+template <class StageNext>
+__device__ __forceinline__ uint32_t crc_batch(const uint32_t *tab, uint8_t *stage, uint32_t c, StageNext stage_next) {
     const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * lane_id());
     uint4 v0, v1, v2, v3;
     asm volatile("s_waitcnt vmcnt(0)\n\t"
@@ -320,7 +335,7 @@ __device__ __forceinline__ uint32_t crc_batch(const uint32_t *tab, uint8_t *stag
                  : "=v"(v0), "=v"(v1), "=v"(v2), "=v"(v3)
                  : "v"(la)
                  : "memory");
-    if (next) crc_stage(stage, next, lastc);
+    stage_next();
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const uint4 x = j < 2 ? v0 : j < 4 ? v1 : j < 6 ? v2 : v3;
@@ -370,26 +385,33 @@ __device__ __forceinline__ uint32_t crc32_ieee_staged(const uint32_t *tab, Cur &
         crc_stage(stage, p + i, lastc);
         while (i + 64 <= n) {
             const bool more = i + 64 < n;
-            c = crc_batch(tab, stage, c, more ? p + i + 64 : nullptr, lastc);
+            c = crc_batch(tab, stage, c, [&] { if (more) crc_stage(stage, p + i + 64, lastc); });
             i += 64;
         }
         if (i < n) c = crc_last(tabaddr, stage, n - i, c);
     }
     return ~c;
 }
-// The same CRC for a message whose 64-byte window [c0, c0 + 64) the walk has
-// just staged into the slot (c0 = the chunk of the message's offset field,
-// p - 16): the CRC's bytes up to c0 + 64 are hashed from the slot, and the
-// first batch from memory is c0 + 64's, staged while they are hashed.
-__device__ __forceinline__ uint32_t crc32_ieee_window(const uint32_t *tab, Cur &cur, const uint8_t *p, uint32_t n,
-                                                      uint8_t *stage, uintptr_t lastc) {
-    const uint32_t tabaddr = (uint32_t)(uintptr_t)tab;
-    uint32_t c = 0xFFFFFFFFu;
-    uint32_t i = crc_head(tabaddr, cur, p, n, c);
-    if (i < n) {
-        const uint8_t *c0 = reinterpret_cast<const uint8_t *>((uintptr_t)(p - 16) & ~(uintptr_t)15);
-        const uint32_t o = (uint32_t)((p + i) - c0);  // 16 or 32
-        if (n - i <= 64 - o) return ~crc_last(tabaddr, stage, o + (n - i), c, o);
+// The same CRC for a message whose window block the walk has in the slot
+// (GRd::win9): the blocks and the bytes hashed of each are ksched::crc_schedule's
+// (kafka_sched.h).  The CRC's bytes in the window block are hashed from the slot,
+// each later block is staged while the one before it is hashed, and the last
+// one stays in the slot for the walk (ksched::keep_base).  b: the request's
+// first byte; wb, p, e: the window block, the CRC's first byte and its end as
+// ksched positions (crc_stage_at), lastr the request's last chunk.
+struct CrcWindowRun {
+    const uint32_t *tab;
+    Cur &cur;
+    const uint8_t *b;
+    uint8_t *stage;
+    uint32_t lastr;
+    uint32_t c;
+    __device__ __forceinline__ uint32_t tabaddr() const { return (uint32_t)(uintptr_t)tab; }
+    __device__ __forceinline__ void head(uint32_t p, uint32_t h) {
+        crc_head(tabaddr(), cur, b + (p - (uint32_t)((uintptr_t)b & 15)), h, c);
+    }
+    __device__ __forceinline__ void slot(uint32_t, uint32_t lo, uint32_t hi) { c = crc_last(tabaddr(), stage, hi, c, lo); }
+    __device__ __forceinline__ void window(uint32_t, uint32_t lo, uint32_t next) {  // lo: 16, 32 or 48
         const uint32_t la = (uint32_t)(uintptr_t)(stage + 16 * lane_id());
         uint4 v1, v2, v3;
         asm volatile("ds_read_b128 %0, %3 offset:1024\n\tds_read_b128 %1, %3 offset:2048\n\t"
@@ -397,24 +419,25 @@ __device__ __forceinline__ uint32_t crc32_ieee_window(const uint32_t *tab, Cur &
                      : "=v"(v1), "=v"(v2), "=v"(v3)
                      : "v"(la)
                      : "memory");
-        crc_stage(stage, c0 + 64, lastc);
-        const uint32_t j0 = o == 16 ? 0 : 2;
+        crc_stage_at(stage, b, next, lastr);
+        const uint32_t j0 = (lo - 16) >> 3;
 #pragma unroll
         for (uint32_t j = 0; j < 6; j++) {
             if (j < j0) continue;
             const uint4 x = j < 2 ? v1 : j < 4 ? v2 : v3;
-            const uint32_t lo = ((j & 1) ? x.z : x.x) ^ c, hi = (j & 1) ? x.w : x.y;
-            c = crc_slice8(tab, lo, hi);
+            const uint32_t lo_ = ((j & 1) ? x.z : x.x) ^ c, hi_ = (j & 1) ? x.w : x.y;
+            c = crc_slice8(tab, lo_, hi_);
         }
-        i += 64 - o;
-        while (i + 64 <= n) {
-            const bool more = i + 64 < n;
-            c = crc_batch(tab, stage, c, more ? p + i + 64 : nullptr, lastc);
-            i += 64;
-        }
-        if (i < n) c = crc_last(tabaddr, stage, n - i, c);
     }
-    return ~c;
+    __device__ __forceinline__ void block(uint32_t, uint32_t next) {
+        c = crc_batch(tab, stage, c, [&] { if (next != ksched::kNoSpan) crc_stage_at(stage, b, next, lastr); });
+    }
+};
+__device__ __forceinline__ uint32_t crc32_ieee_window(const uint32_t *tab, Cur &cur, const uint8_t *b, uint32_t wb,
+                                                      uint32_t p, uint32_t e, uint8_t *stage, uint32_t lastr) {
+    CrcWindowRun run{tab, cur, b, stage, lastr, 0xFFFFFFFFu};
+    ksched::crc_schedule(wb, p, e, run);
+    return ~run.c;
 }
 
 }  // namespace
