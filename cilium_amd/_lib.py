@@ -48,6 +48,8 @@ EXPORTS = (
     "l7g_classify_logged", "l7g_classify_logged_host", "l7g_kafka_api_key_name",
     "l7g_deny_replies", "l7g_deny_replies_host", "l7g_deny_reply_template",
     "l7g_classify_logged_all", "l7g_classify_logged_all_host", "l7g_cass_action_name",
+    "l7g_kafka_sessions_enable", "l7g_kafka_forward", "l7g_kafka_responses", "l7g_kafka_forward_host",
+    "l7g_kafka_responses_host", "l7g_kafka_session_gc", "l7g_kafka_session_reset", "l7g_kafka_session_stats",
 )
 
 
@@ -212,6 +214,18 @@ def load(path=None):
         lib.l7g_deny_replies_host.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, C.POINTER(ReplyOut)]
         lib.l7g_deny_reply_template.restype = vp
         lib.l7g_deny_reply_template.argtypes = [C.c_int, C.POINTER(C.c_size_t)]
+    # (the same for the Kafka sessions: tests/test_kafka_sessions_host.py)
+    if hasattr(lib, "l7g_kafka_sessions_enable"):
+        u64, u32 = C.c_uint64, C.c_uint32
+        lib.l7g_kafka_sessions_enable.argtypes = [vp, u32, cp, sz]
+        lib.l7g_kafka_forward.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, u32, u64, vp, vp, vp]
+        lib.l7g_kafka_responses.argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+        lib.l7g_kafka_forward_host.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, u32, u64, vp, vp]
+        lib.l7g_kafka_responses_host.argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        lib.l7g_kafka_session_gc.argtypes = [vp, u64, u64, C.POINTER(u64)]
+        lib.l7g_kafka_session_reset.argtypes = [vp, vp, u32]
+        lib.l7g_kafka_session_stats.argtypes = [vp, C.POINTER(u64)]
+        lib.l7g_kafka_session_stats.restype = None
     _libs[path] = lib
     return lib
 

@@ -389,6 +389,7 @@ void l7g_engine_destroy(l7g_engine *e) {
     e->scr.clear();
     if (e->d_flow) hipFree(e->d_flow);
     SessionsFree(e);
+    KafkaSessionsFree(e);
     if (e->d_zreg) hipFree(e->d_zreg);
     if (e->zreg_ev) hipEventDestroy(e->zreg_ev);
     for (hipEvent_t ev : e->prof_ev)
@@ -496,6 +497,8 @@ int l7g_conns_set(l7g_engine *e, const l7g_conn_t *conns, uint32_t n, char *err,
     if (!ResolveConns(e, &m)) { set_err(err, errlen, m); return -1; }
     e->sess_reset_all = e->sess.by_id != nullptr;  // every connection is new
     e->sess_reset.clear();
+    e->ksess_reset_all = e->ksess.tab != nullptr;
+    e->ksess_reset.clear();
     return 0;
 }
 
@@ -526,6 +529,7 @@ int l7g_conn_update(l7g_engine *e, uint32_t index, const l7g_conn_t *conn, char 
     e->conns_dirty = true;
     // the new-connection event: proxylib makes a new parser there
     if (e->sess.by_id && !e->sess_reset_all) e->sess_reset.push_back(index);
+    if (e->ksess.tab && !e->ksess_reset_all) e->ksess_reset.push_back(index);
     return 0;
 }
 

@@ -27,7 +27,7 @@ hipError_t WaitLastClassify(l7g_engine *e) {
 // The scratch of stream s (created on first use; past kMaxStreamScratch the
 // least recently used stream's scratch is handed over once s has been made
 // to wait for that stream's last call).  Caller holds e->mu.
-static hipError_t GetScratch(l7g_engine *e, hipStream_t s, StreamScratch **out) {
+hipError_t GetScratch(l7g_engine *e, hipStream_t s, StreamScratch **out) {
     auto it = e->scr.find(s);
     if (it == e->scr.end()) {
         if (e->scr.size() >= kMaxStreamScratch) {

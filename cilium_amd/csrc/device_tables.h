@@ -502,6 +502,55 @@ struct CassSessions {
     unsigned long long *stats;  // CSS_*
 };
 
+// Kafka sessions (l7g_kafka_sessions_enable; kernels/kafka_session.hip): the
+// correlation cache of pkg/kafka/correlation_cache.go, one per connection
+// index, resident in HBM.
+// One per connection index.  Zeroed = a new connection: the next sequence
+// number is seq + 1, so numbering starts at 1.
+struct KafkaSessSlot {  // 8 B
+    uint32_t gen;  // entries claimed under another generation no longer resolve
+    uint32_t seq;  // sequence numbers spent so far (uint32 arithmetic, as the host cache's)
+};
+static_assert(sizeof(KafkaSessSlot) == 8, "KafkaSessSlot layout");
+// One in-flight request of the open-addressed table (linear probing).  claim:
+// 0 = never used (ends a probe chain); kKafkaSessDeleted = answered (claimable,
+// does not end a chain); else (connection + 1) << 32 | generation, which is
+// claimable too once the connection's slot has moved to another generation.
+// The key is (claim, id), the id compared in full.
+constexpr unsigned long long kKafkaSessDeleted = 1ull;  // (no connection: the upper half of a claim is >= 1)
+constexpr uint32_t kKafkaSessNoTaker = 0xFFFFFFFFu;
+struct KafkaSessEntry {  // 40 B
+    unsigned long long claim;
+    uint32_t id;           // the sequence number the request went out under
+    uint32_t orig;         // the client's correlation id
+    int16_t api_key, api_version;
+    uint32_t taker;        // l7g_kafka_responses: the least batch index answering it (kKafkaSessNoTaker: none)
+    uint64_t tag;          // the caller's handle
+    uint64_t created_ms;   // the caller's clock at l7g_kafka_forward
+};
+static_assert(sizeof(KafkaSessEntry) == 40 && offsetof(KafkaSessEntry, tag) == 24, "KafkaSessEntry layout");
+// (KSS_EXPIRED: the last collection's count; the host keeps the sum)
+enum : int { KSS_DROPPED = 0, KSS_FORWARDED = 1, KSS_FOUND = 2, KSS_MISSED = 3, KSS_EXPIRED = 4, KSS_WORDS = 5 };
+struct KafkaSessions {
+    KafkaSessSlot *slots;
+    uint32_t nslots;
+    uint32_t mask;           // table capacity - 1 (a power of two)
+    KafkaSessEntry *tab;     // null: sessions are off
+    KafkaSessEntry *spare;   // l7g_kafka_session_gc compacts into it, then the two swap
+    unsigned long long *stats;  // KSS_*, then two words of the live count
+};
+// One l7g_kafka_forward / l7g_kafka_responses call as its kernels see it: frame
+// i is arena[offs[i] .. offs[i] + lens[i]) on connection conn_ids[i].
+struct KafkaSessBatch {
+    uint8_t *arena;  // (the correlation ids are rewritten in place)
+    uint64_t arena_len;
+    const uint64_t *offs;
+    const uint32_t *lens;
+    const uint32_t *conn_ids;
+    const DevConn *conns;
+    uint32_t n, nconns;
+};
+
 #if defined(__HIPCC__)
 // A lane's large-NFA scratch (2 W words), by its index in the launch
 __device__ __forceinline__ uint64_t *l7_nfa_lane_scratch(uint64_t *base, uint32_t words) {

@@ -58,6 +58,10 @@ struct StreamScratch {
     // l7g_deny_replies: [counters | Kafka index list | scan temporary storage] (bytes, grow-only)
     void *d_reply = nullptr;
     size_t reply_cap = 0;
+    // l7g_kafka_forward: [keys | sorted keys | per-connection segments | sort temporary storage];
+    // l7g_kafka_responses: the entry each response found (bytes, grow-only)
+    void *d_ksess = nullptr;
+    size_t ksess_cap = 0;
     // completion of the last call's kernels on this stream
     hipEvent_t done_ev = nullptr;
     bool launched = false;
@@ -88,7 +92,7 @@ struct StreamScratch {
         if (join_ev) hipEventDestroy(join_ev);
         if (side) hipStreamDestroy(side);
         for (void *p : {(void *)d_bignfa, (void *)d_grp, (void *)d_sel, (void *)d_nfa, (void *)d_hist, d_use, (void *)d_work,
-                        d_reply})
+                        d_reply, d_ksess})
             if (p) hipFree(p);
         if (done_ev) hipEventDestroy(done_ev);
     }
@@ -134,8 +138,14 @@ struct HostCtx {
     // l7g_deny_replies_host: [verdict in | off | len | total | reply bytes], on the device and pinned (grow-only)
     uint8_t *reply_dev = nullptr, *reply_pin = nullptr;
     size_t reply_cap = 0;
+    // l7g_kafka_forward_host / l7g_kafka_responses_host: what the call layout has no place for (the verdicts
+    // and tags in, the per-frame outputs back), on the device and pinned (grow-only)
+    uint8_t *ksess_dev = nullptr, *ksess_pin = nullptr;
+    size_t ksess_cap = 0;
     ~HostCtx() {
         if (s) hipStreamSynchronize(s);
+        if (ksess_dev) hipFree(ksess_dev);
+        if (ksess_pin) hipHostFree(ksess_pin);
         if (log_dev) hipFree(log_dev);
         if (log_pin) hipHostFree(log_pin);
         if (reply_dev) hipFree(reply_dev);
@@ -253,6 +263,12 @@ struct l7g_engine {
     CassSessions sess{};
     std::vector<uint32_t> sess_reset;
     bool sess_reset_all = false;
+    // Kafka sessions (l7g_kafka_sessions_enable; on while ksess.tab is set), kept as the cassandra ones:
+    // the device tables (kernels/kafka_session.hip), one slot per connection index, the pending resets
+    KafkaSessions ksess{};
+    std::vector<uint32_t> ksess_reset;
+    bool ksess_reset_all = false;
+    uint64_t ksess_expired = 0;  // entries l7g_kafka_session_gc dropped since enable
     // Every stream's last completion event (StreamScratch::done_ev) is waited
     // on -- never a caller's stream, which may be gone by then -- before the
     // engine rewrites or frees anything a launched kernel reads: the
@@ -311,6 +327,11 @@ hipError_t WaitLastClassify(l7g_engine *e);  // classify.cc (e->mu held), as Cla
 // capi.cc (e->mu held): with sessions on, a slot for every connection and the pending resets applied
 hipError_t SessionsSync(l7g_engine *e);
 void SessionsFree(l7g_engine *e);
+// kafka_sessions.cc (e->mu held): the same for the Kafka sessions
+hipError_t KafkaSessionsSync(l7g_engine *e);
+void KafkaSessionsFree(l7g_engine *e);
+// classify.cc (e->mu held): the scratch of stream s, the call ordered behind that scratch's last user
+hipError_t GetScratch(l7g_engine *e, hipStream_t s, StreamScratch **out);
 // classify.cc: l7g_cass_replies (device pointers; takes e->mu)
 int CassReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
                 const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream);

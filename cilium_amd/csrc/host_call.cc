@@ -517,4 +517,126 @@ int l7g_cass_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_le
     return (int)rc;
 }
 
+// The Kafka-session staging of the calling thread, grown to `need` bytes.
+static hipError_t KsessGrow(HostCtx *H, size_t need) {
+    if (need <= H->ksess_cap) return hipSuccess;
+    hipStreamSynchronize(H->s);
+    if (H->ksess_dev) hipFree(H->ksess_dev);
+    if (H->ksess_pin) hipHostFree(H->ksess_pin);
+    H->ksess_dev = H->ksess_pin = nullptr;
+    H->ksess_cap = 0;
+    const size_t cap = need + need / 4;
+    hipError_t rc = hipMalloc(&H->ksess_dev, cap);
+    if (rc == hipSuccess) rc = hipHostMalloc(&H->ksess_pin, cap, hipHostMallocDefault);
+    if (rc == hipSuccess) H->ksess_cap = cap;
+    return rc;
+}
+
+static void PutBE32(uint8_t *p, uint32_t v) {
+    p[0] = (uint8_t)(v >> 24);
+    p[1] = (uint8_t)(v >> 16);
+    p[2] = (uint8_t)(v >> 8);
+    p[3] = (uint8_t)v;
+}
+
+// l7g_kafka_forward with host buffers, over the calling thread's stream and
+// staging: the inputs, the verdicts and the tags copied in, the forward
+// kernels, fwd and new_id copied out and waited for.  The arena is not copied
+// back: the caller's frames are patched from new_id, four bytes per forwarded
+// request.  The session staging is [verdict | tag | fwd | new_id].
+int l7g_kafka_forward_host(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                           const uint32_t *conn, const uint8_t *verdict, const uint64_t *tag, uint32_t n,
+                           uint64_t now_ms, uint8_t *fwd, uint32_t *new_id) {
+    if (e->device < 0) return (int)hipErrorNoDevice;
+    if (n && (!off || !len || !conn || !verdict || !fwd || !new_id)) return (int)hipErrorInvalidValue;
+    uint8_t *pa;
+    uint64_t *po;
+    uint32_t *pl, *pc;
+    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
+    if (rc0 != 0) return rc0;
+    if (n) {
+        memcpy(po, off, (size_t)n * 8);
+        memcpy(pl, len, (size_t)n * 4);
+        memcpy(pc, conn, (size_t)n * 4);
+    }
+    if (arena_len) memcpy(pa, arena, arena_len);
+    HostCtx *H = nullptr;
+    hipError_t rc = HostEnter(e, &H);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t o_tag = ((size_t)n + 15) & ~(size_t)15, o_fwd = o_tag + (size_t)n * 8;
+    const size_t o_id = (o_fwd + n + 15) & ~(size_t)15, end = o_id + (size_t)n * 4;
+    if ((rc = KsessGrow(H, end + 16)) != hipSuccess) return (int)rc;
+    const size_t nn = CallNn(n);
+    uint8_t *d_in = H->dev, *d_k = H->ksess_dev, *p_k = H->ksess_pin;
+    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
+    if (rc == hipSuccess && n) {
+        memcpy(p_k, verdict, n);
+        if (tag) memcpy(p_k + o_tag, tag, (size_t)n * 8);
+        rc = hipMemcpyAsync(d_k, p_k, o_fwd, hipMemcpyHostToDevice, H->s);
+    }
+    if (rc == hipSuccess)
+        rc = (hipError_t)l7g_kafka_forward(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
+                                           (const uint32_t *)(d_in + CallLenOff(nn)),
+                                           (const uint32_t *)(d_in + CallConnOff(nn)), d_k,
+                                           tag ? (const uint64_t *)(d_k + o_tag) : nullptr, n, now_ms, d_k + o_fwd,
+                                           (uint32_t *)(d_k + o_id), H->s);
+    if (rc == hipSuccess && n) rc = hipMemcpyAsync(p_k + o_fwd, d_k + o_fwd, end - o_fwd, hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
+    if (rc != hipSuccess || n == 0) return (int)rc;
+    memcpy(fwd, p_k + o_fwd, n);
+    memcpy(new_id, p_k + o_id, (size_t)n * 4);
+    for (uint32_t i = 0; i < n; i++)
+        if (fwd[i] == 1 && len[i] >= 12) PutBE32(arena + off[i] + 8, new_id[i]);
+    return 0;
+}
+
+// l7g_kafka_responses with host buffers, likewise: the inputs copied in, the
+// response kernels, the outputs copied out ([tag | orig_id | api_key |
+// api_version | found] in the session staging), the caller's frames patched
+// from orig_id, four bytes per hit.
+int l7g_kafka_responses_host(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                             const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *found, uint32_t *orig_id,
+                             int16_t *api_key, int16_t *api_version, uint64_t *tag) {
+    if (e->device < 0) return (int)hipErrorNoDevice;
+    if (n && (!off || !len || !conn || !found || !orig_id || !api_key || !api_version || !tag))
+        return (int)hipErrorInvalidValue;
+    uint8_t *pa;
+    uint64_t *po;
+    uint32_t *pl, *pc;
+    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
+    if (rc0 != 0) return rc0;
+    if (n) {
+        memcpy(po, off, (size_t)n * 8);
+        memcpy(pl, len, (size_t)n * 4);
+        memcpy(pc, conn, (size_t)n * 4);
+    }
+    if (arena_len) memcpy(pa, arena, arena_len);
+    HostCtx *H = nullptr;
+    hipError_t rc = HostEnter(e, &H);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t o_orig = (size_t)n * 8, o_key = o_orig + (size_t)n * 4, o_ver = o_key + (size_t)n * 2;
+    const size_t o_found = o_ver + (size_t)n * 2, end = o_found + n;
+    if ((rc = KsessGrow(H, end + 16)) != hipSuccess) return (int)rc;
+    const size_t nn = CallNn(n);
+    uint8_t *d_in = H->dev, *d_k = H->ksess_dev, *p_k = H->ksess_pin;
+    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
+    if (rc == hipSuccess)
+        rc = (hipError_t)l7g_kafka_responses(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
+                                             (const uint32_t *)(d_in + CallLenOff(nn)),
+                                             (const uint32_t *)(d_in + CallConnOff(nn)), n, d_k + o_found,
+                                             (uint32_t *)(d_k + o_orig), (int16_t *)(d_k + o_key),
+                                             (int16_t *)(d_k + o_ver), (uint64_t *)d_k, H->s);
+    if (rc == hipSuccess && n) rc = hipMemcpyAsync(p_k, d_k, end, hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
+    if (rc != hipSuccess || n == 0) return (int)rc;
+    memcpy(tag, p_k, (size_t)n * 8);
+    memcpy(orig_id, p_k + o_orig, (size_t)n * 4);
+    memcpy(api_key, p_k + o_key, (size_t)n * 2);
+    memcpy(api_version, p_k + o_ver, (size_t)n * 2);
+    memcpy(found, p_k + o_found, n);
+    for (uint32_t i = 0; i < n; i++)
+        if (found[i] && len[i] >= 8) PutBE32(arena + off[i] + 4, orig_id[i]);
+    return 0;
+}
+
 }  // extern "C"

@@ -1,0 +1,227 @@
+// Kafka sessions behind the C-ABI (product code): the lifetime of the device
+// tables (kernels/kafka_session.hip) and the calls over device pointers,
+// l7g_kafka_forward and l7g_kafka_responses, each on the caller's stream with
+// that stream's scratch.  Nothing of l7g_classify's plan is involved.  The
+// host-buffer twins are in host_call.cc.
+#include <algorithm>
+#include <cstring>
+
+#include "engine_state.h"
+
+namespace {
+
+void set_err(char *err, size_t errlen, const char *m) {
+    if (err && errlen) {
+        strncpy(err, m, errlen - 1);
+        err[errlen - 1] = 0;
+    }
+}
+
+// Runs `f` (enqueues on the null stream) once no launched kernel can touch the
+// session tables, and waits for it.
+template <class F>
+hipError_t Quiet(l7g_engine *e, F f) {
+    hipError_t rc = WaitLastClassify(e);
+    if (rc == hipSuccess) rc = f();
+    if (rc == hipSuccess) rc = hipStreamSynchronize(nullptr);
+    return rc;
+}
+
+size_t TableBytes(const KafkaSessions &S) { return ((size_t)S.mask + 1) * sizeof(KafkaSessEntry); }
+constexpr size_t kStatBytes = (KSS_WORDS + 2) * sizeof(unsigned long long);
+
+// what every call over a batch starts with (e->mu held): the device, the
+// connection table, the slots and the pending resets
+hipError_t Enter(l7g_engine *e) {
+    if (e->device < 0) return hipErrorNoDevice;
+    if (!e->ksess.tab) return hipErrorNotReady;
+    hipError_t rc = hipSetDevice(e->device);
+    if (rc == hipSuccess) rc = Upload(e);
+    if (rc == hipSuccess) rc = KafkaSessionsSync(e);
+    return rc;
+}
+
+}  // namespace
+
+void KafkaSessionsFree(l7g_engine *e) {
+    for (void *p : {(void *)e->ksess.slots, (void *)e->ksess.tab, (void *)e->ksess.spare, (void *)e->ksess.stats})
+        if (p) hipFree(p);
+    e->ksess = KafkaSessions{};
+    e->ksess_reset.clear();
+    e->ksess_reset_all = false;
+    e->ksess_expired = 0;
+}
+
+hipError_t KafkaSessionsSync(l7g_engine *e) {
+    KafkaSessions &S = e->ksess;
+    if (!S.tab) return hipSuccess;
+    hipError_t rc = hipSuccess;
+    const size_t need = std::max<size_t>(e->conns.size(), 1);
+    if (need > S.nslots) {  // grown with the connection table, the sessions so far kept
+        const size_t cap = std::max(need, (size_t)S.nslots * 2);
+        KafkaSessSlot *d = nullptr;
+        if ((rc = hipMalloc(&d, cap * sizeof(KafkaSessSlot))) != hipSuccess) return rc;
+        rc = Quiet(e, [&] {
+            hipError_t r = hipMemsetAsync(d, 0, cap * sizeof(KafkaSessSlot), nullptr);
+            if (r == hipSuccess && S.nslots)
+                r = hipMemcpyAsync(d, S.slots, (size_t)S.nslots * sizeof(KafkaSessSlot), hipMemcpyDeviceToDevice, nullptr);
+            return r;
+        });
+        if (rc != hipSuccess) { hipFree(d); return rc; }
+        if (S.slots) hipFree(S.slots);
+        S.slots = d;
+        S.nslots = (uint32_t)cap;
+    }
+    if (e->ksess_reset_all) {
+        // every session: zeroed slots and a zeroed table are the state sessions start in
+        rc = Quiet(e, [&] {
+            hipError_t r = hipMemsetAsync(S.slots, 0, (size_t)S.nslots * sizeof(KafkaSessSlot), nullptr);
+            if (r == hipSuccess) r = hipMemsetAsync(S.tab, 0, TableBytes(S), nullptr);
+            return r;
+        });
+    } else if (!e->ksess_reset.empty()) {
+        uint32_t *d = nullptr;
+        const size_t bytes = e->ksess_reset.size() * sizeof(uint32_t);
+        if ((rc = hipMalloc(&d, bytes)) != hipSuccess) return rc;
+        rc = Quiet(e, [&] {
+            hipError_t r = hipMemcpyAsync(d, e->ksess_reset.data(), bytes, hipMemcpyHostToDevice, nullptr);
+            if (r == hipSuccess) r = LaunchKafkaSessReset(S, d, (uint32_t)e->ksess_reset.size(), nullptr);
+            return r;
+        });
+        hipFree(d);
+    }
+    if (rc == hipSuccess) {
+        e->ksess_reset.clear();
+        e->ksess_reset_all = false;
+    }
+    return rc;
+}
+
+extern "C" {
+
+int l7g_kafka_sessions_enable(l7g_engine *e, uint32_t max_inflight, char *err, size_t errlen) {
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->device < 0) { set_err(err, errlen, "a host-only engine keeps no sessions"); return (int)hipErrorNoDevice; }
+    hipError_t rc = hipSetDevice(e->device);
+    if (rc == hipSuccess) rc = WaitLastClassify(e);
+    if (rc != hipSuccess) { set_err(err, errlen, hipGetErrorString(rc)); return (int)rc; }
+    KafkaSessionsFree(e);
+    if (max_inflight == 0) return 0;
+    if (max_inflight > (1u << 28)) { set_err(err, errlen, "max_inflight exceeds 2^28"); return (int)hipErrorInvalidValue; }
+    // open addressing: the power of two that holds twice the requests in flight
+    uint32_t cap = 2;
+    while (cap < 2 * max_inflight) cap <<= 1;
+    KafkaSessions S{};
+    S.mask = cap - 1;
+    const size_t tab = TableBytes(S);
+    rc = hipMalloc(&S.tab, tab);
+    if (rc == hipSuccess) rc = hipMalloc(&S.spare, tab);
+    if (rc == hipSuccess) rc = hipMalloc(&S.stats, kStatBytes);
+    if (rc == hipSuccess) rc = hipMemsetAsync(S.tab, 0, tab, nullptr);
+    if (rc == hipSuccess) rc = hipMemsetAsync(S.stats, 0, kStatBytes, nullptr);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(nullptr);
+    e->ksess = S;  // (the slots come with the first call: KafkaSessionsSync)
+    if (rc != hipSuccess) {
+        KafkaSessionsFree(e);
+        set_err(err, errlen, hipGetErrorString(rc));
+    }
+    return (int)rc;
+}
+
+int l7g_kafka_forward(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                      const uint32_t *conn, const uint8_t *verdict, const uint64_t *tag, uint32_t n, uint64_t now_ms,
+                      uint8_t *fwd, uint32_t *new_id, void *stream) {
+    std::lock_guard<std::mutex> g(e->mu);
+    hipError_t rc = Enter(e);
+    if (rc != hipSuccess || n == 0) return (int)rc;
+    if (!off || !len || !conn || !verdict || !fwd || !new_id) return (int)hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    StreamScratch *S = nullptr;
+    if ((rc = GetScratch(e, s, &S)) != hipSuccess) return (int)rc;
+    const uint32_t nconns = (uint32_t)e->conns.size();
+    const size_t need = KafkaSessForwardScratchBytes(n, nconns);
+    if (need == 0) return (int)hipErrorInvalidValue;
+    if ((rc = S->Grow(&S->d_ksess, &S->ksess_cap, need, need)) != hipSuccess) return (int)rc;
+    const KafkaSessBatch B{arena, arena_len, off, len, conn, e->d_conns, n, nconns};
+    rc = LaunchKafkaSessForward(B, e->ksess, verdict, tag, now_ms, fwd, new_id, S->d_ksess, S->ksess_cap, s);
+    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
+    if (rc == hipSuccess) S->launched = true;
+    return (int)rc;
+}
+
+int l7g_kafka_responses(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                        const uint32_t *conn, uint32_t n, uint8_t *found, uint32_t *orig_id, int16_t *api_key,
+                        int16_t *api_version, uint64_t *tag, void *stream) {
+    std::lock_guard<std::mutex> g(e->mu);
+    hipError_t rc = Enter(e);
+    if (rc != hipSuccess || n == 0) return (int)rc;
+    if (!off || !len || !conn || !found || !orig_id || !api_key || !api_version || !tag) return (int)hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    StreamScratch *S = nullptr;
+    if ((rc = GetScratch(e, s, &S)) != hipSuccess) return (int)rc;
+    const size_t need = KafkaSessResponsesScratchBytes(n);
+    if ((rc = S->Grow(&S->d_ksess, &S->ksess_cap, need, need)) != hipSuccess) return (int)rc;
+    const KafkaSessBatch B{arena, arena_len, off, len, conn, e->d_conns, n, (uint32_t)e->conns.size()};
+    rc = LaunchKafkaSessResponses(B, e->ksess, found, orig_id, api_key, api_version, tag, S->d_ksess, S->ksess_cap, s);
+    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
+    if (rc == hipSuccess) S->launched = true;
+    return (int)rc;
+}
+
+int l7g_kafka_session_gc(l7g_engine *e, uint64_t now_ms, uint64_t lifetime_ms, uint64_t *expired) {
+    std::lock_guard<std::mutex> g(e->mu);
+    if (expired) *expired = 0;
+    hipError_t rc = Enter(e);
+    if (rc != hipSuccess) return (int)rc;
+    KafkaSessions &S = e->ksess;
+    unsigned long long gone = 0;
+    rc = Quiet(e, [&] {
+        hipError_t r = hipMemsetAsync(S.spare, 0, TableBytes(S), nullptr);
+        if (r == hipSuccess) r = hipMemsetAsync(S.stats + KSS_EXPIRED, 0, sizeof gone, nullptr);
+        if (r == hipSuccess) r = LaunchKafkaSessGc(S, now_ms, lifetime_ms, S.stats + KSS_EXPIRED, nullptr);
+        if (r == hipSuccess) r = hipMemcpyAsync(&gone, S.stats + KSS_EXPIRED, sizeof gone, hipMemcpyDeviceToHost, nullptr);
+        return r;
+    });
+    if (rc != hipSuccess) return (int)rc;
+    std::swap(S.tab, S.spare);
+    e->ksess_expired += gone;
+    if (expired) *expired = gone;
+    return 0;
+}
+
+int l7g_kafka_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n) {
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->device < 0) return (int)hipErrorNoDevice;
+    if (!e->ksess.tab) return (int)hipErrorNotReady;
+    if (!e->ksess_reset_all) e->ksess_reset.insert(e->ksess_reset.end(), conn, conn + n);
+    hipError_t rc = hipSetDevice(e->device);
+    if (rc == hipSuccess) rc = KafkaSessionsSync(e);
+    return (int)rc;
+}
+
+void l7g_kafka_session_stats(l7g_engine *e, uint64_t out[7]) {
+    std::lock_guard<std::mutex> g(e->mu);
+    for (int k = 0; k < 7; k++) out[k] = 0;
+    if (e->device < 0 || !e->ksess.tab) return;
+    KafkaSessions &S = e->ksess;
+    unsigned long long h[KSS_WORDS + 2] = {};
+    hipError_t rc = hipSetDevice(e->device);
+    if (rc == hipSuccess) rc = KafkaSessionsSync(e);
+    if (rc == hipSuccess)
+        rc = Quiet(e, [&] {
+            hipError_t r = hipMemsetAsync(S.stats + KSS_WORDS, 0, 2 * sizeof(unsigned long long), nullptr);
+            if (r == hipSuccess) r = LaunchKafkaSessLive(S, S.stats + KSS_WORDS, nullptr);
+            if (r == hipSuccess) r = hipMemcpyAsync(h, S.stats, sizeof h, hipMemcpyDeviceToHost, nullptr);
+            return r;
+        });
+    if (rc != hipSuccess) return;
+    out[0] = h[KSS_WORDS];
+    out[1] = h[KSS_WORDS + 1];
+    out[2] = h[KSS_DROPPED];
+    out[3] = h[KSS_FORWARDED];
+    out[4] = h[KSS_FOUND];
+    out[5] = h[KSS_MISSED];
+    out[6] = e->ksess_expired;
+}
+
+}  // extern "C"

@@ -58,6 +58,21 @@ hipError_t LaunchCassandraReplies(const Batch &B, const CassSessions &S, void *s
                                   hipStream_t stream);
 hipError_t LaunchCassandraSessionReset(const CassSessions &S, const uint32_t *conn, uint32_t n, hipStream_t stream);
 hipError_t LaunchCassandraSessionLive(const CassSessions &S, unsigned long long *out2, hipStream_t stream);
+// Kafka sessions (kernels/kafka_session.hip): l7g_kafka_forward, l7g_kafka_responses and the table's upkeep;
+// scratch: the ...ScratchBytes of the call (0: the batch is too large), 256-byte aligned
+size_t KafkaSessForwardScratchBytes(uint32_t n, uint32_t nconns);
+hipError_t LaunchKafkaSessForward(const KafkaSessBatch &B, const KafkaSessions &S, const uint8_t *verdict,
+                                  const uint64_t *tag, uint64_t now_ms, uint8_t *fwd, uint32_t *new_id, void *scratch,
+                                  size_t scratch_bytes, hipStream_t stream);
+size_t KafkaSessResponsesScratchBytes(uint32_t n);
+hipError_t LaunchKafkaSessResponses(const KafkaSessBatch &B, const KafkaSessions &S, uint8_t *found, uint32_t *orig_id,
+                                    int16_t *api_key, int16_t *api_version, uint64_t *tag, void *scratch,
+                                    size_t scratch_bytes, hipStream_t stream);
+// S.spare zeroed by the caller, who swaps the tables afterwards; *expired is added to
+hipError_t LaunchKafkaSessGc(const KafkaSessions &S, uint64_t now_ms, uint64_t lifetime_ms, unsigned long long *expired,
+                             hipStream_t stream);
+hipError_t LaunchKafkaSessReset(const KafkaSessions &S, const uint32_t *conn, uint32_t n, hipStream_t stream);
+hipError_t LaunchKafkaSessLive(const KafkaSessions &S, unsigned long long *out2, hipStream_t stream);
 hipError_t LaunchCounters(const uint8_t *verdict, const int32_t *rule, uint32_t n, uint32_t nrules,
                           uint64_t *counters, uint32_t *scratch, hipStream_t stream);
 size_t CountersScratchBytes();

@@ -336,6 +336,97 @@ class Engine:
         self._lib.l7g_cass_session_stats(self._h, out)
         return dict(zip(self.SESSION_STATS, [int(x) for x in out]))
 
+    # -------------------------------------------------------- kafka sessions
+    def kafka_sessions(self, max_inflight):
+        """Device-resident Kafka correlation caches (l7g_kafka_sessions_enable):
+        with max_inflight > 0 the engine renumbers forwarded requests and
+        correlates responses per connection; 0 turns that off."""
+        err = C.create_string_buffer(512)
+        rc = self._lib.l7g_kafka_sessions_enable(self._h, int(max_inflight), err, 512)
+        if rc != 0:
+            raise RuntimeError(f"l7g_kafka_sessions_enable: HIP error {rc}: " + err.value.decode(errors="replace"))
+
+    def kafka_forward(self, arena, offsets, lengths, conn_ids, verdict, now_ms, tags=None):
+        """HandleRequest over a batch (host buffers): the ids of the forwarded
+        requests are rewritten in `arena` (a writable contiguous uint8 array);
+        returns (fwd, new_id)."""
+        if not (isinstance(arena, np.ndarray) and arena.dtype == np.uint8 and arena.flags.c_contiguous
+                and arena.flags.writeable):
+            raise TypeError("arena: a writable contiguous uint8 array (it is rewritten in place)")
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        v = np.ascontiguousarray(verdict, dtype=np.uint8)
+        tg = None if tags is None else np.ascontiguousarray(tags, dtype=np.uint64)
+        n = len(off)
+        fwd = np.zeros(n, np.uint8)
+        new_id = np.zeros(n, np.uint32)
+        rc = self._lib.l7g_kafka_forward_host(self._h, arena.ctypes.data, arena.nbytes, off.ctypes.data, ln.ctypes.data,
+                                              cid.ctypes.data, v.ctypes.data, None if tg is None else tg.ctypes.data, n,
+                                              int(now_ms), fwd.ctypes.data, new_id.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"l7g_kafka_forward_host failed: HIP error {rc}")
+        return fwd, new_id
+
+    def kafka_forward_device(self, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, verdict_ptr, tag_ptr, n, now_ms,
+                             fwd_ptr, new_id_ptr, stream=0):
+        """l7g_kafka_forward: all pointers are device addresses (tag_ptr may be 0)."""
+        rc = self._lib.l7g_kafka_forward(self._h, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, verdict_ptr,
+                                         tag_ptr or None, n, int(now_ms), fwd_ptr, new_id_ptr, stream or None)
+        if rc != 0:
+            raise RuntimeError(f"l7g_kafka_forward failed: HIP error {rc}")
+
+    def kafka_responses(self, arena, offsets, lengths, conn_ids):
+        """CorrelateResponse over a batch (host buffers): the original ids are
+        restored in `arena`; returns (found, orig_id, api_key, api_version, tag)."""
+        if not (isinstance(arena, np.ndarray) and arena.dtype == np.uint8 and arena.flags.c_contiguous
+                and arena.flags.writeable):
+            raise TypeError("arena: a writable contiguous uint8 array (it is rewritten in place)")
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        n = len(off)
+        found = np.zeros(n, np.uint8)
+        orig = np.zeros(n, np.uint32)
+        key = np.zeros(n, np.int16)
+        ver = np.zeros(n, np.int16)
+        tag = np.zeros(n, np.uint64)
+        rc = self._lib.l7g_kafka_responses_host(self._h, arena.ctypes.data, arena.nbytes, off.ctypes.data,
+                                                ln.ctypes.data, cid.ctypes.data, n, found.ctypes.data, orig.ctypes.data,
+                                                key.ctypes.data, ver.ctypes.data, tag.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"l7g_kafka_responses_host failed: HIP error {rc}")
+        return found, orig, key, ver, tag
+
+    def kafka_responses_device(self, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, found_ptr, orig_id_ptr,
+                               api_key_ptr, api_version_ptr, tag_ptr, stream=0):
+        """l7g_kafka_responses: all pointers are device addresses."""
+        rc = self._lib.l7g_kafka_responses(self._h, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, found_ptr,
+                                           orig_id_ptr, api_key_ptr, api_version_ptr, tag_ptr, stream or None)
+        if rc != 0:
+            raise RuntimeError(f"l7g_kafka_responses failed: HIP error {rc}")
+
+    def kafka_session_gc(self, now_ms, lifetime_ms):
+        """Drops the entries older than lifetime_ms at now_ms and compacts the table; returns how many."""
+        gone = C.c_uint64(0)
+        rc = self._lib.l7g_kafka_session_gc(self._h, int(now_ms), int(lifetime_ms), C.byref(gone))
+        if rc != 0:
+            raise RuntimeError(f"l7g_kafka_session_gc failed: HIP error {rc}")
+        return int(gone.value)
+
+    def kafka_session_reset(self, conn_ids):
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        rc = self._lib.l7g_kafka_session_reset(self._h, cid.ctypes.data, len(cid))
+        if rc != 0:
+            raise RuntimeError(f"l7g_kafka_session_reset failed: HIP error {rc}")
+
+    KAFKA_SESSION_STATS = ("live", "used_slots", "dropped", "forwarded", "found", "missed", "expired")
+
+    def kafka_session_stats(self):
+        out = (C.c_uint64 * 7)()
+        self._lib.l7g_kafka_session_stats(self._h, out)
+        return dict(zip(self.KAFKA_SESSION_STATS, [int(x) for x in out]))
+
     def conn_update(self, index, conn):
         """One connection set (or added) alone: l7g_conn_update, the new-connection event."""
         arr = conns_array([conn])

@@ -1282,3 +1282,88 @@ def cassandra_session_script(nconns=64, rounds=30, nreq=256, nrep=96, seed=None)
                 reps.append(cass_frame(0x08, (4).to_bytes(4, "big") + b"\x00\x02ab", int(rng.integers(0, 6))))  # request direction
         out.append({"requests": reqs, "req_conn": rc, "replies": reps, "rep_conn": pc})
     return conns, cassandra_policy(), out
+
+
+def kafka_response_frame(corr, body=b"\x00\x00"):
+    """A size-prefixed broker response: the correlation id, then `body`."""
+    return struct.pack(">iI", 4 + len(body), corr & 0xFFFFFFFF) + body
+
+
+def kafka_session_script(nconns=64, rounds=30, nreq=256, nrep=96, seed=None):
+    """A correlation script: (conns, policy, rounds); each round is a dict with
+    one request batch (requests, req_conn, verdict, tags, now_ms) and the
+    response batch that follows it (responses, rep_conn).  Every eighth
+    connection has no parser (protocol 0), a few requests name no connection at all.  Requests:
+    Produce, Fetch, Metadata, ListOffsets, OffsetCommit and an untyped kind,
+    some cut below 12 bytes, with a verdict mix (mostly ALLOW).  Responses carry
+    ids as a cache numbering from 1 per connection issues them -- the script
+    keeps that numbering itself, for the ALLOWed requests of Kafka connections
+    -- : ids in flight, ids already answered, ids never issued, duplicates
+    within the batch and frames shorter than 8 bytes.  Deterministic in seed."""
+    seed = SEED_BASE + 37 if seed is None else seed
+    rng = np.random.default_rng(seed)
+    conns = make_conns(nconns, 0, 9092, True, PROTO_KAFKA, ([7, 8, 100, 101] * (nconns // 4 + 1))[:nconns])
+    conns["proto"][7::8] = 0
+    is_kafka = conns["proto"] == PROTO_KAFKA
+    topics = kafka_topics()
+    nxt = [1] * nconns                          # the next sequence number of each connection
+    flight = [list() for _ in range(nconns)]    # ids issued and not yet answered
+    done = [list() for _ in range(nconns)]      # ids answered
+    out = []
+    for r in range(rounds):
+        rc = rng.integers(0, nconns, size=nreq).astype(np.uint32)
+        rc[rng.random(nreq) < 0.01] = nconns + int(rng.integers(0, 1000))
+        verdict = rng.choice(np.array([1, 1, 1, 1, 1, 1, 0, 0, 2, 3, 4], np.uint8), size=nreq)
+        tags = rng.integers(1, 1 << 63, size=nreq, dtype=np.uint64)
+        reqs = []
+        for i, c in enumerate(rc.tolist()):
+            corr = int(rng.integers(0, 1 << 32))
+            if corr >= 1 << 31:
+                corr -= 1 << 32
+            t = topics[int(rng.integers(0, len(topics)))]
+            k = int(rng.integers(0, 8))
+            client = "c%d" % int(rng.integers(0, 100000))   # (its length moves the next frame's alignment)
+            if k == 0:
+                f = k_produce(int(rng.integers(0, 3)), corr, client, [(t, [(0, [k_message(b"v" * int(rng.integers(1, 9)))])])])
+            elif k == 1:
+                f = k_fetch(int(rng.integers(0, 6)), corr, client, [(t, [0, 1])])
+            elif k == 2:
+                f = k_metadata(int(rng.integers(0, 5)), corr, client, [t])
+            elif k == 3:
+                f = k_offset(int(rng.integers(0, 3)), corr, client, [(t, [0])])
+            elif k == 4:
+                f = k_offset_commit(int(rng.integers(0, 3)), corr, client, "g", [(t, [0])])
+            elif k == 5:
+                f = k_request(18, int(rng.integers(0, 3)), corr, client, b"")   # ApiVersions: untyped
+            elif k == 6:
+                f = k_fetch(4, corr, client, [(t, [2])])
+            else:
+                f = k_metadata(1, corr, client, [t])[:int(rng.integers(0, 12))]   # below the id's end
+            reqs.append(f)
+            if verdict[i] == 1 and c < nconns and is_kafka[c]:
+                flight[c].append(nxt[c])
+                nxt[c] = (nxt[c] + 1) & 0xFFFFFFFF
+        pc = rng.integers(0, nconns, size=nrep).astype(np.uint32)
+        reps = []
+        for j, c in enumerate(pc.tolist()):
+            k = float(rng.random())
+            body = b"\x00" * int(rng.integers(0, 7))
+            if k < 0.55 and flight[c]:
+                cid = flight[c].pop(int(rng.integers(0, len(flight[c]))))
+                done[c].append(cid)
+                reps.append(kafka_response_frame(cid, body))
+            elif k < 0.67 and done[c]:
+                reps.append(kafka_response_frame(done[c][int(rng.integers(0, len(done[c])))], body))
+            elif k < 0.77:
+                reps.append(kafka_response_frame(nxt[c] + int(rng.integers(0, 1 << 20)), body))    # never issued
+            elif k < 0.89 and j:
+                d = int(rng.integers(0, j))                                                      # a duplicate: same
+                pc[j] = pc[d]                                                                    # connection, same id
+                reps.append(reps[d][:8] + body if len(reps[d]) >= 8 else reps[d])
+            elif k < 0.95:
+                reps.append(kafka_response_frame(1, body)[:int(rng.integers(0, 8))])             # no id: reads as 0
+            else:
+                reps.append(kafka_response_frame(0, body))
+        out.append({"requests": reqs, "req_conn": rc, "verdict": verdict, "tags": tags, "now_ms": 1000 * (r + 1),
+                    "responses": reps, "rep_conn": pc})
+    return conns, cfg3_policy(), out

@@ -499,6 +499,102 @@ int l7g_cass_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_le
 int l7g_cass_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n);
 void l7g_cass_session_stats(l7g_engine *e, uint64_t out[6]);
 
+/* Kafka sessions (off by default): the correlation cache of the in-agent Kafka
+ * proxy (pkg/kafka/correlation_cache.go) for device-resident batches, one
+ * session per connection index.  A post-pass: l7g_classify and its kernels are
+ * not involved.  l7g_kafka_corr_* stays the host path for small calls.
+ *
+ * l7g_kafka_sessions_enable: max_inflight > 0 turns them on (again: all
+ * sessions start empty), 0 turns them off and frees the tables.  One
+ * open-addressed table of 40-byte entries is allocated, its capacity the power
+ * of two that is at least 2 x max_inflight (at most 2^28 in flight), a second
+ * one of the same size for l7g_kafka_session_gc to compact into, and one
+ * 8-byte slot per connection index (a generation and the next sequence number,
+ * starting at 1), grown with the connection table.  A host-only engine returns
+ * hipErrorNoDevice.  While sessions are off the other calls return
+ * hipErrorNotReady.
+ *
+ * l7g_kafka_forward is HandleRequest (correlation_cache.go:116-147) for a
+ * batch: n frames on device memory as l7g_classify took them, size prefix
+ * included, at any byte alignment, with the verdicts it gave.  Request i is
+ * forwarded iff verdict[i] == L7G_ALLOW, conn[i] is a valid connection index
+ * whose protocol is Kafka, and the frame lies inside the arena.  The forwarded
+ * requests of one connection are numbered in batch order: the k-th of them (k
+ * from 0) gets id next + k in uint32 arithmetic, and the connection's next
+ * advances by their count.  With len >= 12 the original id is big-endian bytes
+ * 8..12 (pkg/kafka/request.go:57-70) and those four bytes are overwritten in
+ * the arena with the new id -- no other byte of the arena is written; with
+ * len < 12 the original id is 0 and nothing is written, but the entry is made
+ * all the same.  The entry keeps the original id, the api key (bytes 4..6) and
+ * version (bytes 6..8; 0 for what a shorter frame lacks), tag[i] (0 when tag
+ * is NULL: the caller's handle on whatever else its response log record
+ * needs, in place of the reference's *RequestMessage) and now_ms.
+ *   fwd[i]: 0 not forwarded; 1 rewritten and cached; 2 the table had no free
+ *   slot: the bytes are untouched, nothing is cached, the sequence number is
+ *   spent, and the caller must not send this request under this session.
+ *   new_id[i]: the new id when fwd[i] == 1, else 0.
+ * The access-log record of a request carries the client's id
+ * (pkg/proxy/kafka.go:169-181 runs before HandleRequest), so
+ * l7g_classify_logged and l7g_deny_replies go before l7g_kafka_forward on the
+ * stream.  An id repeats only after 2^32 forwards on one connection; a request
+ * still in flight by then is out of contract.
+ *
+ * l7g_kafka_responses is CorrelateResponse (:158-178) for a batch of
+ * size-prefixed response frames.  The id is big-endian bytes 4..8 if len >= 8,
+ * else 0 (pkg/kafka/response.go:33-46).  A live entry of (conn[i], id) is a
+ * hit: the original id is restored in place (if len >= 8), the entry is
+ * forgotten, found[i] = 1 and orig_id, api_key, api_version and tag are those
+ * of the request.  A miss leaves the bytes alone and sets found[i] and the
+ * other outputs to 0; a connection that is invalid or not Kafka is a miss.
+ * When several responses of one batch carry one id on one connection, the
+ * earliest in batch order is the hit and the others are misses, as in the
+ * reference's loop.
+ *
+ * The _host twins take host buffers on the calling thread's stream: inputs
+ * staged as for l7g_classify_host, the small outputs copied back, the
+ * caller's arena patched from new_id / orig_id (four bytes per hit) instead of
+ * copied back; they synchronise.
+ *
+ * l7g_kafka_session_gc drops every entry with now_ms - created_ms >=
+ * lifetime_ms (an entry from after now_ms has age 0; the reference's
+ * RequestLifetime is 5 minutes, the clock is the caller's), re-inserts the
+ * others into the second table and swaps the two, so that answered and stale
+ * slots are gone as well: afterwards stats [1] == [0].  *expired (may be NULL)
+ * is the number dropped.  Waits for the launched calls.  Without it the
+ * never-used slots run out under churn and a miss then costs a probe of the
+ * whole table -- correct, but slow: watch [1] against the capacity.
+ *
+ * Resets: l7g_conn_update(index) is the new-connection event: that
+ * connection's entries stop resolving and its numbering restarts at 1;
+ * l7g_conns_set empties all; l7g_kafka_session_reset empties the named ones.
+ * A policy update resets nothing.  Resets are applied before the next launch.
+ *
+ * The state is engine-wide, not per stream: calls that touch one connection
+ * must be ordered by the caller, by issuing them on one stream; calls over
+ * disjoint connections may use different streams.
+ *
+ * l7g_kafka_session_stats: [0] live entries, [1] table slots that are not
+ * never-used (live + answered + stale), [2] inserts dropped (table full), [3]
+ * requests forwarded (fwd 1), [4] responses found, [5] responses missed, [6]
+ * entries expired; [2..6] since sessions were enabled.  Waits for the
+ * launched calls.  A host-only engine, or sessions off: zeros. */
+int l7g_kafka_sessions_enable(l7g_engine *e, uint32_t max_inflight, char *err, size_t errlen);
+int l7g_kafka_forward(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                      const uint32_t *conn, const uint8_t *verdict, const uint64_t *tag /* may be NULL */, uint32_t n,
+                      uint64_t now_ms, uint8_t *fwd, uint32_t *new_id, void *stream);
+int l7g_kafka_responses(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                        const uint32_t *conn, uint32_t n, uint8_t *found, uint32_t *orig_id, int16_t *api_key,
+                        int16_t *api_version, uint64_t *tag, void *stream);
+int l7g_kafka_forward_host(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                           const uint32_t *conn, const uint8_t *verdict, const uint64_t *tag, uint32_t n,
+                           uint64_t now_ms, uint8_t *fwd, uint32_t *new_id);
+int l7g_kafka_responses_host(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                             const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *found, uint32_t *orig_id,
+                             int16_t *api_key, int16_t *api_version, uint64_t *tag);
+int l7g_kafka_session_gc(l7g_engine *e, uint64_t now_ms, uint64_t lifetime_ms, uint64_t *expired);
+int l7g_kafka_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n);
+void l7g_kafka_session_stats(l7g_engine *e, uint64_t out[7]);
+
 /* Resident services: the synchronous drop-in calls of l7g_classify_host (and
  * so the Envoy adapter's Allowed() and proxylib's OnData) whose requests are
  * all HTTP (at most 8) or all memcached (at most 64) are posted to one polling
