@@ -5,6 +5,12 @@ sets (messages.go:460-489); verdicts bit-exact against the oracle.
 The reference holds no compressed vectors: parity unpinned beyond the oracle
 restatement, which tests/test_kafka_compressed_host.py pins against zlib and
 against the same requests sent uncompressed.
+
+The inner sets here are well-formed, and a decoded message with a wrong CRC
+ends its set silently, so these tests pin that the device decodes, not what it
+decodes.  The decoded bytes are pinned by tests/test_gpu_kafka_inflate_content.py,
+whose streams end each decoded set with a message that fails the request when
+the walk reaches it.
 """
 import gzip
 import struct
