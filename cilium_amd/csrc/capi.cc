@@ -1,8 +1,9 @@
 // C-ABI implementation (include/l7gpu.h): engine lifetime, policy versions,
 // compiled tables across ranks, the connection table and its upload, and the
 // statistics, profile and debug exports (product code).  The launch plan is
-// classify.cc, the host-buffer calls host_call.cc, the resident services
-// service.cc; engine_state.h holds what they share.
+// classify.cc, the session tables cass_sessions.cc and kafka_sessions.cc, the
+// host-buffer calls host_call.cc, the resident services service.cc;
+// engine_state.h holds what they share.
 #include <algorithm>
 #include <cstring>
 
@@ -14,13 +15,6 @@
 #include "regex/re_dfa.h"
 
 namespace {
-
-void set_err(char *err, size_t errlen, const std::string &m) {
-    if (!err || errlen == 0) return;
-    size_t n = std::min(errlen - 1, m.size());
-    memcpy(err, m.data(), n);
-    err[n] = 0;
-}
 
 template <class T>
 size_t Put(std::vector<uint8_t> &blob, const std::vector<T> &v) {
@@ -258,74 +252,6 @@ hipError_t Upload(l7g_engine *e) {
     return hipSuccess;
 }
 
-// ---- cassandra sessions: the device tables' lifetime (caller holds e->mu)
-namespace {
-// Runs `f` (enqueues on the null stream) once no launched kernel can touch the
-// session tables, and waits for it.
-template <class F>
-hipError_t SessionsQuiet(l7g_engine *e, F f) {
-    hipError_t rc = WaitLastClassify(e);
-    if (rc == hipSuccess) rc = f();
-    if (rc == hipSuccess) rc = hipStreamSynchronize(nullptr);
-    return rc;
-}
-}  // namespace
-
-void SessionsFree(l7g_engine *e) {
-    for (void *p : {(void *)e->sess.slots, (void *)e->sess.by_stream, (void *)e->sess.by_id, (void *)e->sess.stats})
-        if (p) hipFree(p);
-    e->sess = CassSessions{};
-    e->sess_reset.clear();
-    e->sess_reset_all = false;
-}
-
-hipError_t SessionsSync(l7g_engine *e) {
-    CassSessions &S = e->sess;
-    if (!S.by_id) return hipSuccess;
-    hipError_t rc = hipSuccess;
-    const size_t need = std::max<size_t>(e->conns.size(), 1);
-    if (need > S.nslots) {  // grown with the connection table, the sessions so far kept
-        const size_t cap = std::max(need, (size_t)S.nslots * 2);
-        CassSlot *d = nullptr;
-        if ((rc = hipMalloc(&d, cap * sizeof(CassSlot))) != hipSuccess) return rc;
-        rc = SessionsQuiet(e, [&] {
-            hipError_t r = hipMemsetAsync(d, 0, cap * sizeof(CassSlot), nullptr);
-            if (r == hipSuccess && S.nslots)
-                r = hipMemcpyAsync(d, S.slots, (size_t)S.nslots * sizeof(CassSlot), hipMemcpyDeviceToDevice, nullptr);
-            return r;
-        });
-        if (rc != hipSuccess) { hipFree(d); return rc; }
-        if (S.slots) hipFree(S.slots);
-        S.slots = d;
-        S.nslots = (uint32_t)cap;
-    }
-    if (e->sess_reset_all) {
-        // every session: zeroed slots and tables are the state sessions start in
-        const size_t tab = ((size_t)S.mask + 1) * sizeof(CassEntry);
-        rc = SessionsQuiet(e, [&] {
-            hipError_t r = hipMemsetAsync(S.slots, 0, (size_t)S.nslots * sizeof(CassSlot), nullptr);
-            if (r == hipSuccess) r = hipMemsetAsync(S.by_stream, 0, tab, nullptr);
-            if (r == hipSuccess) r = hipMemsetAsync(S.by_id, 0, tab, nullptr);
-            return r;
-        });
-    } else if (!e->sess_reset.empty()) {
-        uint32_t *d = nullptr;
-        const size_t bytes = e->sess_reset.size() * sizeof(uint32_t);
-        if ((rc = hipMalloc(&d, bytes)) != hipSuccess) return rc;
-        rc = SessionsQuiet(e, [&] {
-            hipError_t r = hipMemcpyAsync(d, e->sess_reset.data(), bytes, hipMemcpyHostToDevice, nullptr);
-            if (r == hipSuccess) r = LaunchCassandraSessionReset(S, d, (uint32_t)e->sess_reset.size(), nullptr);
-            return r;
-        });
-        hipFree(d);
-    }
-    if (rc == hipSuccess) {
-        e->sess_reset.clear();
-        e->sess_reset_all = false;
-    }
-    return rc;
-}
-
 // capi_internal.h: proto_form 0 = JSON, 1 = NPDS DiscoveryResponse; proxylib
 // != 0 = the proxylib instance's update (instance.go:168-219), which also
 // NACKs what only proxylib's policymap rejects (PolicySet::px_nack).
@@ -531,67 +457,6 @@ int l7g_conn_update(l7g_engine *e, uint32_t index, const l7g_conn_t *conn, char 
     if (e->sess.by_id && !e->sess_reset_all) e->sess_reset.push_back(index);
     if (e->ksess.tab && !e->ksess_reset_all) e->ksess_reset.push_back(index);
     return 0;
-}
-
-int l7g_cass_sessions_enable(l7g_engine *e, uint32_t max_statements, char *err, size_t errlen) {
-    std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) { set_err(err, errlen, "a host-only engine keeps no sessions"); return (int)hipErrorNoDevice; }
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = WaitLastClassify(e);
-    if (rc != hipSuccess) { set_err(err, errlen, hipGetErrorString(rc)); return (int)rc; }
-    SessionsFree(e);
-    if (max_statements == 0) return 0;
-    // open addressing: twice the statements, so that probe chains stay short when all are held
-    if (max_statements > (1u << 24)) { set_err(err, errlen, "max_statements exceeds 2^24"); return (int)hipErrorInvalidValue; }
-    uint32_t cap = 16;
-    while (cap < 2 * max_statements) cap <<= 1;
-    CassSessions S{};
-    S.mask = cap - 1;
-    const size_t tab = (size_t)cap * sizeof(CassEntry), st = (CSS_WORDS + 2) * sizeof(unsigned long long);
-    rc = hipMalloc(&S.by_stream, tab);
-    if (rc == hipSuccess) rc = hipMalloc(&S.by_id, tab);
-    if (rc == hipSuccess) rc = hipMalloc(&S.stats, st);
-    if (rc == hipSuccess) rc = hipMemsetAsync(S.by_stream, 0, tab, nullptr);
-    if (rc == hipSuccess) rc = hipMemsetAsync(S.by_id, 0, tab, nullptr);
-    if (rc == hipSuccess) rc = hipMemsetAsync(S.stats, 0, st, nullptr);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(nullptr);
-    e->sess = S;  // (the slots come with the first launch: SessionsSync)
-    if (rc != hipSuccess) {
-        SessionsFree(e);
-        set_err(err, errlen, hipGetErrorString(rc));
-    }
-    return (int)rc;
-}
-
-int l7g_cass_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n) {
-    std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) return (int)hipErrorNoDevice;
-    if (!e->sess.by_id) return (int)hipErrorNotReady;
-    if (!e->sess_reset_all) e->sess_reset.insert(e->sess_reset.end(), conn, conn + n);
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = SessionsSync(e);
-    return (int)rc;
-}
-
-void l7g_cass_session_stats(l7g_engine *e, uint64_t out[6]) {
-    std::lock_guard<std::mutex> g(e->mu);
-    for (int k = 0; k < 6; k++) out[k] = 0;
-    if (e->device < 0 || !e->sess.by_id) return;
-    unsigned long long h[CSS_WORDS + 2] = {};
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = SessionsSync(e);
-    if (rc == hipSuccess) rc = WaitLastClassify(e);
-    if (rc == hipSuccess) rc = hipMemsetAsync(e->sess.stats + CSS_WORDS, 0, 2 * sizeof(unsigned long long), nullptr);
-    if (rc == hipSuccess) rc = LaunchCassandraSessionLive(e->sess, e->sess.stats + CSS_WORDS, nullptr);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(h, e->sess.stats, sizeof h, hipMemcpyDeviceToHost, nullptr);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(nullptr);
-    if (rc != hipSuccess) return;
-    out[0] = h[CSS_WORDS];
-    out[1] = h[CSS_WORDS + 1];
-    out[2] = h[CSS_DROPPED];
-    out[3] = h[CSS_OVERFLOW];
-    out[4] = h[CSS_RESOLVED];
-    out[5] = h[CSS_UNPREPARED];
 }
 
 // the access-log record's layout as the kernels write it (LogRec / LogSpan, device_tables.h)

@@ -60,7 +60,23 @@ hipError_t GetScratch(l7g_engine *e, hipStream_t s, StreamScratch **out) {
     return hipSuccess;
 }
 
-// l7g_classify; host_conn: the connection indices in host memory as well
+hipError_t CallBegin(l7g_engine *e, unsigned sync, hipStream_t s, StreamScratch **scratch) {
+    hipError_t rc = hipSetDevice(e->device);
+    if (rc == hipSuccess) rc = Upload(e);
+    if (rc == hipSuccess && (sync & kSyncCass)) rc = SessionsSync(e);
+    if (rc == hipSuccess && (sync & kSyncKafka)) rc = KafkaSessionsSync(e);
+    if (rc == hipSuccess && scratch) rc = GetScratch(e, s, scratch);
+    return rc;
+}
+
+hipError_t CallEnd(StreamScratch *S, hipStream_t s, hipError_t rc) {
+    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
+    if (rc == hipSuccess) S->launched = true;
+    return rc;
+}
+
+// l7g_classify over the call frame (in, out; o: what the other callers add);
+// host_conn: the connection indices in host memory as well
 // (l7g_classify_host's calls), so that a small call whose requests all use the
 // hot HTTP rule set skips the general HTTP kernel's launch
 // pre: the call's inputs still to be copied from pinned host memory to where
@@ -72,22 +88,24 @@ hipError_t GetScratch(l7g_engine *e, hipStream_t s, StreamScratch **out) {
 // text: l7g_classify_logged_all's (with log): the logged plan, with
 // http_log_kernel moved before the cassandra step and generic_log_kernel after
 // the cassandra classifier -- with sessions, before that call's commit.
-int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
-             const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed, uint64_t *counters,
-             void *stream, const uint32_t *host_conn, const CopyIn *pre, bool *signaled, const LogOut *log,
-             const LogText *text) {
+int Classify(l7g_engine *e, const DevIn &in, const DevOut &out, void *stream, const ClassifyOpts &o) {
+    const uint32_t n = in.n;
+    uint64_t *const counters = out.counters;
+    const uint32_t *const host_conn = o.host_conn;
+    const CopyIn *const pre = o.pre;
+    const LogOut *const log = o.log;
+    const LogText *const text = o.text;
     std::lock_guard<std::mutex> g(e->mu);
     if (e->device < 0) return (int)hipErrorNoDevice;
     if (log && (!log->rec || ((uintptr_t)log->rec & 15) || (log->stride && !log->topics) || pre))
         return (int)hipErrorInvalidValue;
     if (text && (!log || (text->stride && !text->text))) return (int)hipErrorInvalidValue;
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = Upload(e);
-    if (rc == hipSuccess) rc = SessionsSync(e);
-    if (rc != hipSuccess) return (int)rc;
     hipStream_t s = (hipStream_t)stream;
-    const Batch B{arena, arena_len, off, len, conn, e->d_conns, verdict, rule, consumed, n, (uint32_t)e->conns.size()};
-    if (n == 0) return 0;
+    StreamScratch *S = nullptr;
+    hipError_t rc = CallBegin(e, kSyncCass, s, n ? &S : nullptr);
+    if (rc != hipSuccess || n == 0) return (int)rc;
+    const Batch B{in.arena, in.arena_len, in.off, in.len, in.conn, e->d_conns, out.verdict, out.rule, out.consumed,
+                  n, (uint32_t)e->conns.size()};
     // The kernels each classify only their own protocol's requests, so a
     // mixed batch needs one launch per protocol present.  When the engine
     // serves more than one protocol, partition_kernel runs first: it writes
@@ -121,8 +139,6 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
         }
     }
     if (n >= kPartitionMin) ReleaseServiceCUs(e);  // (persistent grids: every CU)
-    StreamScratch *S = nullptr;
-    if ((rc = GetScratch(e, s, &S)) != hipSuccess) return (int)rc;
     uint32_t *sel_k = nullptr, *sel_z = nullptr, *cnt = nullptr;
     ListEnt *sel_m = nullptr, *sel_h = nullptr;
     if (partitioned) {
@@ -201,7 +217,7 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
     }
     if (fuse_http) fuse_http = &fused_c;
     if (fuse_mc) fuse_mc = &fused_c;
-    if (signaled) *signaled = signal;
+    if (o.signaled) *o.signaled = signal;
     const bool run[4] = {partitioned, run_http, run_kafka, run_mc};
     for (int k = 0; k < 4; k++) e->prof_ran[k] = run[k];
     mark(0);
@@ -344,61 +360,31 @@ int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint
     // per-rule allow hits and per-verdict totals, from the outputs
     if (rc == hipSuccess && counters) {
         if (!S->d_hist) rc = hipMalloc(&S->d_hist, CountersScratchBytes());
-        if (rc == hipSuccess) rc = LaunchCounters(verdict, rule, n, (uint32_t)e->ps->nrules, counters, S->d_hist, s);
+        if (rc == hipSuccess)
+            rc = LaunchCounters(out.verdict, out.rule, n, (uint32_t)e->ps->nrules, counters, S->d_hist, s);
     }
-    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
-    if (rc == hipSuccess) S->launched = true;
-    return (int)rc;
-}
-
-// l7g_cass_replies: the replies framed, the RESULT/prepared ones bound, on the
-// caller's stream with that stream's cassandra scratch.
-int CassReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
-                const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream) {
-    std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) return (int)hipErrorNoDevice;
-    if (!e->sess.by_id) return (int)hipErrorNotReady;  // sessions are off: nothing to bind into
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = Upload(e);
-    if (rc == hipSuccess) rc = SessionsSync(e);
-    if (rc != hipSuccess || n == 0) return (int)rc;
-    hipStream_t s = (hipStream_t)stream;
-    StreamScratch *S = nullptr;
-    if ((rc = GetScratch(e, s, &S)) != hipSuccess) return (int)rc;
-    const size_t need = CassandraScratchBytes(n);
-    if (need == 0) return (int)hipErrorInvalidValue;
-    rc = S->Grow(&S->d_use, &S->use_cap, need, need);
-    const Batch B{arena, arena_len, off, len, conn, e->d_conns, verdict, nullptr, consumed, n, (uint32_t)e->conns.size()};
-    if (rc == hipSuccess) rc = LaunchCassandraReplies(B, e->sess, S->d_use, S->use_cap, s);
-    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
-    if (rc == hipSuccess) S->launched = true;
-    return (int)rc;
+    return (int)CallEnd(S, s, rc);
 }
 
 // l7g_deny_replies: the post-pass over a classified batch, on the caller's
 // stream with that stream's reply scratch.  Nothing of l7g_classify's plan is
 // involved: the kernels read the verdicts and the connection table.
-int DenyReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
-                const uint32_t *conn, uint32_t n, const uint8_t *verdict, const l7g_reply_out_t *out, void *stream) {
+int DenyReplies(l7g_engine *e, const DevIn &in, const uint8_t *verdict, const l7g_reply_out_t *out, void *stream) {
     std::lock_guard<std::mutex> g(e->mu);
     if (e->device < 0) return (int)hipErrorNoDevice;
     if (!out || !out->off || !out->len || !out->total || (!out->buf && out->cap)) return (int)hipErrorInvalidValue;
-    if (n && (!off || !len || !conn || !verdict)) return (int)hipErrorInvalidValue;
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = Upload(e);  // (the connection table the kernels read)
-    if (rc != hipSuccess) return (int)rc;
+    if (in.n && (!in.off || !in.len || !in.conn || !verdict)) return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
     StreamScratch *S = nullptr;
-    if ((rc = GetScratch(e, s, &S)) != hipSuccess) return (int)rc;
-    const size_t need = DenyRepliesScratchBytes(n);
+    hipError_t rc = CallBegin(e, kSyncNone, s, &S);  // (the connection table the kernels read)
+    if (rc != hipSuccess) return (int)rc;
+    const size_t need = DenyRepliesScratchBytes(in.n);
     if (need == 0) return (int)hipErrorInvalidValue;
     if ((rc = S->Grow(&S->d_reply, &S->reply_cap, need, need)) != hipSuccess) return (int)rc;
-    const Batch B{arena, arena_len, off, len, conn, e->d_conns, const_cast<uint8_t *>(verdict), nullptr, nullptr, n,
-                  (uint32_t)e->conns.size()};
+    const Batch B{in.arena, in.arena_len, in.off, in.len, in.conn, e->d_conns, const_cast<uint8_t *>(verdict), nullptr,
+                  nullptr, in.n, (uint32_t)e->conns.size()};
     rc = LaunchDenyReplies(B, out->buf, out->cap, out->off, out->len, out->total, S->d_reply, S->reply_cap, s);
-    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
-    if (rc == hipSuccess) S->launched = true;
-    return (int)rc;
+    return (int)CallEnd(S, s, rc);
 }
 
 extern "C" {
@@ -406,7 +392,7 @@ extern "C" {
 int l7g_deny_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
                      const uint32_t *conn, uint32_t n, const uint8_t *verdict, const l7g_reply_out_t *out,
                      void *stream) {
-    return DenyReplies(e, arena, arena_len, off, len, conn, n, verdict, out, stream);
+    return DenyReplies(e, {arena, arena_len, off, len, conn, n}, verdict, out, stream);
 }
 
 const uint8_t *l7g_deny_reply_template(int proto, size_t *len) {
@@ -419,15 +405,10 @@ const uint8_t *l7g_deny_reply_template(int proto, size_t *len) {
     return p;
 }
 
-int l7g_cass_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
-                     const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream) {
-    return CassReplies(e, arena, arena_len, off, len, conn, n, verdict, consumed, stream);
-}
-
 int l7g_classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
                  const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed,
                  uint64_t *counters, void *stream) {
-    return Classify(e, arena, arena_len, off, len, conn, n, verdict, rule, consumed, counters, stream, nullptr);
+    return Classify(e, {arena, arena_len, off, len, conn, n}, {verdict, rule, consumed, counters}, stream);
 }
 
 int l7g_classify_logged(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
@@ -435,8 +416,9 @@ int l7g_classify_logged(l7g_engine *e, const uint8_t *arena, uint64_t arena_len,
                         uint32_t *consumed, uint64_t *counters, const l7g_log_out_t *log, void *stream) {
     if (!log) return (int)hipErrorInvalidValue;
     const LogOut lo{reinterpret_cast<LogRec *>(log->rec), reinterpret_cast<LogSpan *>(log->topics), log->topic_stride};
-    return Classify(e, arena, arena_len, off, len, conn, n, verdict, rule, consumed, counters, stream, nullptr, nullptr,
-                    nullptr, &lo);
+    ClassifyOpts o;
+    o.log = &lo;
+    return Classify(e, {arena, arena_len, off, len, conn, n}, {verdict, rule, consumed, counters}, stream, o);
 }
 
 int l7g_classify_logged_all(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
@@ -445,8 +427,10 @@ int l7g_classify_logged_all(l7g_engine *e, const uint8_t *arena, uint64_t arena_
     if (!log) return (int)hipErrorInvalidValue;
     const LogOut lo{reinterpret_cast<LogRec *>(log->rec), reinterpret_cast<LogSpan *>(log->spans), log->span_stride};
     const LogText tx{log->text, log->text_stride};
-    return Classify(e, arena, arena_len, off, len, conn, n, verdict, rule, consumed, counters, stream, nullptr, nullptr,
-                    nullptr, &lo, &tx);
+    ClassifyOpts o;
+    o.log = &lo;
+    o.text = &tx;
+    return Classify(e, {arena, arena_len, off, len, conn, n}, {verdict, rule, consumed, counters}, stream, o);
 }
 
 int l7g_frame_streams(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *s_off,
@@ -471,8 +455,8 @@ int l7g_classify_streams(l7g_engine *e, const uint8_t *arena, uint64_t arena_len
                                frame_conn, nframes, stream);
     if (rc != 0) return rc;
     // every slot, the empty ones on connection ~0 (answered UNSUPPORTED)
-    return Classify(e, arena, arena_len, frame_off, frame_len, frame_conn, n * max_frames, verdict, rule, consumed,
-                    counters, stream, nullptr);
+    return Classify(e, {arena, arena_len, frame_off, frame_len, frame_conn, n * max_frames},
+                    {verdict, rule, consumed, counters}, stream);
 }
 
 }  // extern "C"

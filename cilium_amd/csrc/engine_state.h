@@ -1,12 +1,17 @@
 // The engine behind the C-ABI (include/l7gpu.h): its state, the thresholds of
 // its launch plan, and the few internals shared by capi.cc (lifetime, policy,
-// tables, connections, statistics), classify.cc (the launch plan), host_call.cc
-// (the per-thread host staging path) and service.cc (the resident services).
+// tables, connections, statistics), classify.cc (the launch plan and the call
+// frame of every device-pointer entry: DevIn, DevOut, CallBegin, CallEnd),
+// cass_sessions.cc and kafka_sessions.cc (the session tables; their shared
+// lifetime is sessions.h), host_call.cc (the per-thread host staging path:
+// HostCtx, StagePair, CallViews) and service.cc (the resident services).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -114,6 +119,34 @@ constexpr uint32_t kLatencyMax = 64;
 constexpr uint32_t kGroupMin = 1u << 16;
 constexpr size_t kNfaScratchBytes = 256ull << 20;  // large NFAs: state-set scratch per stream (lanes in flight)
 
+// A grow-only buffer on the device with its pinned host twin: what a
+// host-buffer call stages beside the call layout (HostCtx below).
+struct StagePair {
+    uint8_t *dev = nullptr, *pin = nullptr;
+    size_t cap = 0;  // bytes of each; 0 after a failed allocation
+    // At least `need` bytes of each.  The stream's last call may still use the
+    // old ones: it ends before they are freed.  (some slack: batches vary)
+    hipError_t Grow(hipStream_t s, size_t need) {
+        if (need <= cap) return hipSuccess;
+        hipStreamSynchronize(s);
+        Free();
+        const size_t c = need + need / 4;
+        hipError_t rc = hipMalloc(&dev, c);
+        if (rc == hipSuccess) rc = hipHostMalloc(&pin, c, hipHostMallocDefault);
+        if (rc == hipSuccess) cap = c;
+        return rc;
+    }
+    void Free() {
+        if (dev) hipFree(dev);
+        if (pin) hipHostFree(pin);
+        dev = pin = nullptr;
+        cap = 0;
+    }
+    StagePair() = default;
+    StagePair(const StagePair &) = delete;
+    ~StagePair() { Free(); }
+};
+
 // l7g_classify_host's per-thread staging: its own stream, device arena and
 // request arrays (grow-only), so host-buffer calls from different threads
 // overlap instead of queueing on one stream.
@@ -132,24 +165,15 @@ struct HostCtx {
     uint32_t *pin_done_dev = nullptr;
     uint32_t seq = 0;
     size_t in_cap = 0, out_cap = 0;
-    // l7g_classify_logged_host: [records | topic rows], on the device and pinned (grow-only)
-    uint8_t *log_dev = nullptr, *log_pin = nullptr;
-    size_t log_cap = 0;
-    // l7g_deny_replies_host: [verdict in | off | len | total | reply bytes], on the device and pinned (grow-only)
-    uint8_t *reply_dev = nullptr, *reply_pin = nullptr;
-    size_t reply_cap = 0;
+    // l7g_classify_logged_host, l7g_classify_logged_all_host: [records | span rows | text rows]
+    StagePair log;
+    // l7g_deny_replies_host: [verdict in | off | len | total | reply bytes]
+    StagePair reply;
     // l7g_kafka_forward_host / l7g_kafka_responses_host: what the call layout has no place for (the verdicts
-    // and tags in, the per-frame outputs back), on the device and pinned (grow-only)
-    uint8_t *ksess_dev = nullptr, *ksess_pin = nullptr;
-    size_t ksess_cap = 0;
-    ~HostCtx() {
+    // and tags in, the per-frame outputs back)
+    StagePair ksess;
+    ~HostCtx() {  // (the three pairs free themselves after this, the stream idle by then)
         if (s) hipStreamSynchronize(s);
-        if (ksess_dev) hipFree(ksess_dev);
-        if (ksess_pin) hipHostFree(ksess_pin);
-        if (log_dev) hipFree(log_dev);
-        if (log_pin) hipHostFree(log_pin);
-        if (reply_dev) hipFree(reply_dev);
-        if (reply_pin) hipHostFree(reply_pin);
         if (dev) hipFree(dev);
         if (pin_in) hipHostFree(pin_in);
         if (pin_out) hipHostFree(pin_out);
@@ -167,6 +191,39 @@ struct HostIn {
     size_t stride;  // > 0: len and conn lie at CallLenOff(stride) and CallConnOff(stride) from off
     const l7g_host_seg *seg;
     int nseg;  // the arena is these pieces, concatenated
+};
+
+// The inputs of a call as its kernels see them: request i is arena[off[i] ..
+// off[i] + len[i]) on connection conn[i].  Device pointers (host_call.cc's
+// HostStage takes a caller's host arrays in the same form).
+struct DevIn {
+    const uint8_t *arena;
+    uint64_t arena_len;
+    const uint64_t *off;
+    const uint32_t *len, *conn;
+    uint32_t n;
+};
+// The views of call-layout inputs (kernels/call_layout.h) that start at `base`,
+// the three arrays `stride` entries long: a staging on the device, or the
+// pinned one.
+inline DevIn CallViews(const uint8_t *base, size_t stride, uint64_t arena_len, uint32_t n) {
+    return {base + CallArenaOff(stride), arena_len, (const uint64_t *)base, (const uint32_t *)(base + CallLenOff(stride)),
+            (const uint32_t *)(base + CallConnOff(stride)), n};
+}
+// l7g_classify's outputs (device pointers; counters may be null)
+struct DevOut {
+    uint8_t *verdict;
+    int32_t *rule;
+    uint32_t *consumed;
+    uint64_t *counters;
+};
+// What a caller of Classify other than l7g_classify adds (classify.cc)
+struct ClassifyOpts {
+    const uint32_t *host_conn = nullptr;  // the connection indices in host memory as well
+    const CopyIn *pre = nullptr;          // the inputs' copy from pinned memory, still to be done
+    bool *signaled = nullptr;             // out: the call's last kernel stores pre->done
+    const LogOut *log = nullptr;          // l7g_classify_logged's outputs
+    const LogText *text = nullptr;        // l7g_classify_logged_all's (with log)
 };
 
 // ---- resident services (kernels/service.h): the synchronous drop-in calls
@@ -322,9 +379,17 @@ inline bool SpinUntil(Load load, uint32_t seq, std::chrono::milliseconds limit) 
     }
 }
 
+// an error message into a caller's buffer (truncated to fit)
+inline void set_err(char *err, size_t errlen, const std::string &m) {
+    if (!err || errlen == 0) return;
+    size_t n = std::min(errlen - 1, m.size());
+    memcpy(err, m.data(), n);
+    err[n] = 0;
+}
+
 hipError_t Upload(l7g_engine *e);            // capi.cc (e->mu held)
 hipError_t WaitLastClassify(l7g_engine *e);  // classify.cc (e->mu held), as Classify (takes e->mu)
-// capi.cc (e->mu held): with sessions on, a slot for every connection and the pending resets applied
+// cass_sessions.cc (e->mu held): with sessions on, a slot for every connection and the pending resets applied
 hipError_t SessionsSync(l7g_engine *e);
 void SessionsFree(l7g_engine *e);
 // kafka_sessions.cc (e->mu held): the same for the Kafka sessions
@@ -332,16 +397,18 @@ hipError_t KafkaSessionsSync(l7g_engine *e);
 void KafkaSessionsFree(l7g_engine *e);
 // classify.cc (e->mu held): the scratch of stream s, the call ordered behind that scratch's last user
 hipError_t GetScratch(l7g_engine *e, hipStream_t s, StreamScratch **out);
-// classify.cc: l7g_cass_replies (device pointers; takes e->mu)
-int CassReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
-                const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed, void *stream);
-int Classify(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
-             const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed, uint64_t *counters,
-             void *stream, const uint32_t *host_conn, const CopyIn *pre = nullptr, bool *signaled = nullptr,
-             const LogOut *log = nullptr, const LogText *text = nullptr);
+// classify.cc (e->mu held, the entry's own checks passed): what every call over a batch starts with -- the
+// device, the tables and connections uploaded, the named sessions synced, and (scratch not null) GetScratch --
+// and ends with: done_ev recorded behind the call's launches, which WaitLastClassify waits on.
+enum : unsigned { kSyncNone = 0, kSyncCass = 1, kSyncKafka = 2 };
+hipError_t CallBegin(l7g_engine *e, unsigned sync, hipStream_t s, StreamScratch **scratch);
+hipError_t CallEnd(StreamScratch *S, hipStream_t s, hipError_t rc);
+// classify.cc: l7g_classify and its logged forms (device pointers; takes e->mu)
+int Classify(l7g_engine *e, const DevIn &in, const DevOut &out, void *stream, const ClassifyOpts &o = {});
+// cass_sessions.cc: l7g_cass_replies (device pointers; takes e->mu)
+int CassReplies(l7g_engine *e, const DevIn &in, uint8_t *verdict, uint32_t *consumed, void *stream);
 // classify.cc: l7g_deny_replies (device pointers; takes e->mu)
-int DenyReplies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
-                const uint32_t *conn, uint32_t n, const uint8_t *verdict, const l7g_reply_out_t *out, void *stream);
+int DenyReplies(l7g_engine *e, const DevIn &in, const uint8_t *verdict, const l7g_reply_out_t *out, void *stream);
 void StopServices(l7g_engine *e);  // service.cc, as the next two
 void ReleaseServiceCUs(l7g_engine *e);
 bool ServiceTry(l7g_engine *e, uint32_t n, uint64_t arena_len, const HostIn &in, uint8_t *verdict, int32_t *rule,

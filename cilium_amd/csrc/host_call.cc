@@ -1,11 +1,17 @@
 // l7g_classify_host's per-thread path (product code), in three steps: stage,
 // fill, run (the batcher's flushers fill the staging in place and skip the
-// copy).  The staging's layout is kernels/call_layout.h.
+// copy).  The staging's layout is kernels/call_layout.h.  The host-buffer twins
+// of the other calls follow: each starts with HostStage, sends the staging
+// over with UploadStaged, calls its device-pointer entry on the views
+// (CallViews, OutViews) and fills the caller's arrays (UnpackOut); what the
+// call layout has no place for travels in a StagePair of the thread's HostCtx
+// (engine_state.h).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "engine_state.h"
+#include "wire.h"
 
 // grow-only staging for the inputs and the outputs of a call
 static hipError_t HostGrow(HostCtx *H, uint32_t n, uint64_t arena_len) {
@@ -59,6 +65,41 @@ static hipError_t HostEnter(l7g_engine *e, HostCtx **H, bool grow = false, uint3
     return grow ? HostGrow(*H, n, arena_len) : hipSuccess;
 }
 
+// What every host-buffer twin starts with: the thread's context entered (once),
+// its staging grown, the caller's arrays and arena (`host`: host pointers)
+// copied into the pinned staging.  *dev: the views of the device staging that
+// UploadStaged fills from it.
+static hipError_t HostStage(l7g_engine *e, const DevIn &host, HostCtx **Hout, DevIn *dev) {
+    HostCtx *H = nullptr;
+    const hipError_t rc = HostEnter(e, &H, true, host.n, host.arena_len);
+    if (rc != hipSuccess) return rc;
+    const size_t nn = CallNn(host.n), n = host.n;
+    if (n) {
+        memcpy(H->pin_in, host.off, n * 8);
+        memcpy(H->pin_in + CallLenOff(nn), host.len, n * 4);
+        memcpy(H->pin_in + CallConnOff(nn), host.conn, n * 4);
+    }
+    if (host.arena_len) memcpy(H->pin_in + CallArenaOff(nn), host.arena, host.arena_len);
+    *Hout = H;
+    *dev = CallViews(H->dev, nn, host.arena_len, host.n);
+    return hipSuccess;
+}
+// the staged inputs to the device: one copy of the whole layout
+static hipError_t UploadStaged(HostCtx *H, const DevIn &dev) {
+    return hipMemcpyAsync(H->dev, H->pin_in, CallInBytes(CallNn(dev.n), dev.arena_len), hipMemcpyHostToDevice, H->s);
+}
+
+// A call's outputs (call_layout.h) at d_out, and the caller's arrays filled
+// from the pinned ones (rule null: a call without rules).
+static DevOut OutViews(uint8_t *d_out, uint32_t n) {
+    return {d_out, (int32_t *)(d_out + CallRuleOff(n)), (uint32_t *)(d_out + CallConsumedOff(n)), nullptr};
+}
+static void UnpackOut(const HostCtx *H, uint32_t n, uint8_t *verdict, int32_t *rule, uint32_t *consumed) {
+    memcpy(verdict, H->pin_out, n);
+    if (rule) memcpy(rule, H->pin_out + CallRuleOff(n), (size_t)n * 4);
+    memcpy(consumed, H->pin_out + CallConsumedOff(n), (size_t)n * 4);
+}
+
 // classify a call whose inputs are in pinned host memory, wait for it, copy
 // the answers out
 static hipError_t HostRun(l7g_engine *e, HostCtx *H, uint32_t n, uint64_t arena_len, const HostIn &in,
@@ -78,9 +119,7 @@ static hipError_t HostRun(l7g_engine *e, HostCtx *H, uint32_t n, uint64_t arena_
     const bool zc = zc_on && (in.nseg == 0 || (in.nseg == 1 && in.seg[0].rows <= 1)) && n <= kZeroCopyMaxRequests &&
                     a_off + arena_len <= kZeroCopyMaxBytes;
     hipStream_t s = H->s;
-    const uint64_t *d_o;
-    const uint32_t *d_l, *d_c;
-    const uint8_t *d_a;
+    DevIn dv;  // the inputs where the kernels read them
     uint8_t *d_out = H->dev + H->in_cap;
     CopyIn pre{};  // zero-copy: the inputs' copy into HBM, done by the call's first kernel
     if (zc) {
@@ -98,10 +137,8 @@ static hipError_t HostRun(l7g_engine *e, HostCtx *H, uint32_t n, uint64_t arena_
             // the thread's staging (packed): one piece
             ci.p[0] = {H->pin_in_dev, d_in, (uint64_t)CallInBytes(nn, arena_len)};
             ci.n = 1;
-            d_o = (const uint64_t *)d_in;
-            d_l = (const uint32_t *)(d_in + CallLenOff(nn));
-            d_c = (const uint32_t *)(d_in + CallConnOff(nn));
-            d_a = d_in + a_at;
+            dv = CallViews(d_in, nn, arena_len, n);
+            dv.arena = d_in + a_at;
         } else {
             // a batcher slot: four pieces into [off | len | conn | arena], the arrays
             // nn4 entries long so each starts 16-byte aligned (call_layout.h)
@@ -121,10 +158,8 @@ static hipError_t HostRun(l7g_engine *e, HostCtx *H, uint32_t n, uint64_t arena_
             ci.p[2] = {h_c, d_in + CallConnOff(nn4), (uint64_t)nn * 4};
             ci.p[3] = {h_a, d_in + a_off, in.nseg ? arena_len : 0};
             ci.n = 4;
-            d_o = (const uint64_t *)d_in;
-            d_l = (const uint32_t *)(d_in + CallLenOff(nn4));
-            d_c = (const uint32_t *)(d_in + CallConnOff(nn4));
-            d_a = in.nseg ? d_in + a_off : d_in;
+            dv = CallViews(d_in, nn4, arena_len, n);
+            dv.arena = in.nseg ? d_in + a_off : d_in;
         }
         pre = ci;
         pre.done = H->pin_done_dev;
@@ -133,40 +168,36 @@ static hipError_t HostRun(l7g_engine *e, HostCtx *H, uint32_t n, uint64_t arena_
         uint8_t *d_in = H->dev;
         const bool staging = in.off == (const uint64_t *)H->pin_in;
         const size_t st = staging ? nn : in.stride ? in.stride : nn;
-        d_o = (const uint64_t *)d_in;
-        d_l = (const uint32_t *)(d_in + CallLenOff(st));
-        d_c = (const uint32_t *)(d_in + CallConnOff(st));
-        d_a = d_in + CallArenaOff((uint32_t)st);
+        dv = CallViews(d_in, st, arena_len, n);
+        uint8_t *d_a = d_in + CallArenaOff(st);
         if (staging) {  // the thread's staging: one copy of the whole layout
             rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, s);
         } else {
             if (in.stride) {  // the three arrays in one copy
                 rc = hipMemcpyAsync(d_in, in.off, CallConnOff(st) + (size_t)n * 4, hipMemcpyHostToDevice, s);
             } else {
-                rc = hipMemcpyAsync((void *)d_o, in.off, (size_t)n * 8, hipMemcpyHostToDevice, s);
-                if (rc == hipSuccess) rc = hipMemcpyAsync((void *)d_l, in.len, (size_t)n * 4, hipMemcpyHostToDevice, s);
-                if (rc == hipSuccess) rc = hipMemcpyAsync((void *)d_c, in.conn, (size_t)n * 4, hipMemcpyHostToDevice, s);
+                rc = hipMemcpyAsync((void *)dv.off, in.off, (size_t)n * 8, hipMemcpyHostToDevice, s);
+                if (rc == hipSuccess) rc = hipMemcpyAsync((void *)dv.len, in.len, (size_t)n * 4, hipMemcpyHostToDevice, s);
+                if (rc == hipSuccess) rc = hipMemcpyAsync((void *)dv.conn, in.conn, (size_t)n * 4, hipMemcpyHostToDevice, s);
             }
             uint64_t at = 0;
             for (int k = 0; k < in.nseg && rc == hipSuccess; k++) {
                 const l7g_host_seg &g = in.seg[k];
                 if (!g.width || !g.rows) continue;
                 if (g.rows == 1)
-                    rc = hipMemcpyAsync((void *)(d_a + at), g.p, g.width, hipMemcpyHostToDevice, s);
+                    rc = hipMemcpyAsync(d_a + at, g.p, g.width, hipMemcpyHostToDevice, s);
                 else
-                    rc = hipMemcpy2DAsync((void *)(d_a + at), g.width, g.p, g.pitch, g.width, g.rows,
-                                          hipMemcpyHostToDevice, s);
+                    rc = hipMemcpy2DAsync(d_a + at, g.width, g.p, g.pitch, g.width, g.rows, hipMemcpyHostToDevice, s);
                 at += g.width * g.rows;
             }
         }
     }
-    uint8_t *d_v = d_out;
-    int32_t *d_r = (int32_t *)(d_out + CallRuleOff(n));
-    uint32_t *d_cons = (uint32_t *)(d_out + CallConsumedOff(n));
     bool signaled = false;
-    if (rc == hipSuccess)
-        rc = (hipError_t)Classify(e, d_a, arena_len, d_o, d_l, d_c, n, d_v, d_r, d_cons, nullptr, s, in.conn,
-                                  pre.n ? &pre : nullptr, &signaled);
+    ClassifyOpts o;
+    o.host_conn = in.conn;
+    o.pre = pre.n ? &pre : nullptr;
+    o.signaled = &signaled;
+    if (rc == hipSuccess) rc = (hipError_t)Classify(e, dv, OutViews(d_out, n), s, o);
     if (rc == hipSuccess && n && !zc)
         rc = hipMemcpyAsync(H->pin_out, d_out, CallOutBytes(n), hipMemcpyDeviceToHost, s);
     // One workgroup answered the call: its done word says the answers are in
@@ -179,12 +210,7 @@ static hipError_t HostRun(l7g_engine *e, HostCtx *H, uint32_t n, uint64_t arena_
         std::atomic_thread_fence(std::memory_order_acquire);
     }
     if (rc == hipSuccess && !done) rc = hipStreamSynchronize(s);
-    if (rc == hipSuccess && n) {
-        const uint8_t *po = H->pin_out;
-        memcpy(verdict, po, n);
-        memcpy(rule, po + CallRuleOff(n), (size_t)n * 4);
-        memcpy(consumed, po + CallConsumedOff(n), (size_t)n * 4);
-    }
+    if (rc == hipSuccess && n) UnpackOut(H, n, verdict, rule, consumed);
     return rc;
 }
 
@@ -193,30 +219,29 @@ int l7g_host_stage(l7g_engine *e, uint32_t n, uint64_t arena_len, uint8_t **aren
     HostCtx *H = nullptr;
     const hipError_t rc = HostEnter(e, &H, true, n, arena_len);
     if (rc != hipSuccess) return (int)rc;
-    const size_t nn = CallNn(n);
-    *off = (uint64_t *)H->pin_in;
-    *len = (uint32_t *)(H->pin_in + CallLenOff(nn));
-    *conn = (uint32_t *)(H->pin_in + CallConnOff(nn));
-    *arena = H->pin_in + CallArenaOff(nn);
+    const DevIn p = CallViews(H->pin_in, CallNn(n), arena_len, n);
+    *off = (uint64_t *)p.off;
+    *len = (uint32_t *)p.len;
+    *conn = (uint32_t *)p.conn;
+    *arena = (uint8_t *)p.arena;
     return 0;
 }
 
-static int HostRunStaged(l7g_engine *e, uint32_t n, uint64_t arena_len, uint8_t *verdict, int32_t *rule,
-                         uint32_t *consumed, bool try_service) {
-    HostCtx *H = nullptr;
-    hipError_t rc = HostEnter(e, &H);
-    if (rc == hipSuccess) {
-        const size_t nn = CallNn(n);
-        const l7g_host_seg seg{H->pin_in + CallArenaOff(nn), arena_len, arena_len, 1};
-        const HostIn in{(const uint64_t *)H->pin_in, (const uint32_t *)(H->pin_in + CallLenOff(nn)),
-                        (const uint32_t *)(H->pin_in + CallConnOff(nn)), nn, &seg, 1};
-        rc = HostRun(e, H, n, arena_len, in, verdict, rule, consumed, try_service);
-    }
-    return (int)rc;
+// HostRun over the thread's filled staging
+static hipError_t HostRunStaged(l7g_engine *e, HostCtx *H, uint32_t n, uint64_t arena_len, uint8_t *verdict,
+                                int32_t *rule, uint32_t *consumed, bool try_service) {
+    const size_t nn = CallNn(n);
+    const DevIn p = CallViews(H->pin_in, nn, arena_len, n);
+    const l7g_host_seg seg{p.arena, arena_len, arena_len, 1};
+    const HostIn in{p.off, p.len, p.conn, nn, &seg, 1};
+    return HostRun(e, H, n, arena_len, in, verdict, rule, consumed, try_service);
 }
 
 int l7g_host_run(l7g_engine *e, uint32_t n, uint64_t arena_len, uint8_t *verdict, int32_t *rule, uint32_t *consumed) {
-    return HostRunStaged(e, n, arena_len, verdict, rule, consumed, true);
+    HostCtx *H = nullptr;
+    hipError_t rc = HostEnter(e, &H);
+    if (rc == hipSuccess) rc = HostRunStaged(e, H, n, arena_len, verdict, rule, consumed, true);
+    return (int)rc;
 }
 int l7g_host_run_pinned(l7g_engine *e, uint32_t n, const uint64_t *off, size_t stride, const l7g_host_seg *seg,
                         int nseg, uint8_t *verdict, int32_t *rule, uint32_t *consumed) {
@@ -227,9 +252,8 @@ int l7g_host_run_pinned(l7g_engine *e, uint32_t n, const uint64_t *off, size_t s
     // device staging for `st` entries' arrays and the arena, pinned outputs for n
     hipError_t rc = HostEnter(e, &H, true, st, arena_len);
     if (rc == hipSuccess) {
-        const uint8_t *b = (const uint8_t *)off;
-        const HostIn in{off, (const uint32_t *)(b + CallLenOff(stride)), (const uint32_t *)(b + CallConnOff(stride)),
-                        stride, seg, nseg};
+        const DevIn p = CallViews((const uint8_t *)off, stride, arena_len, n);
+        const HostIn in{off, p.len, p.conn, stride, seg, nseg};
         rc = HostRun(e, H, n, arena_len, in, verdict, rule, consumed);
     }
     return (int)rc;
@@ -260,145 +284,73 @@ int l7g_classify_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, c
         hipError_t rc = hipSuccess;
         if (e->device >= 0 && ServiceTry(e, n, arena_len, in, verdict, rule, consumed, &rc)) return (int)rc;
     }
-    uint8_t *pa;
-    uint64_t *po;
-    uint32_t *pl, *pc;
-    int rc = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
-    if (rc != 0) return rc;
-    if (n) {
-        memcpy(po, off, (size_t)n * 8);
-        memcpy(pl, len, (size_t)n * 4);
-        memcpy(pc, conn, (size_t)n * 4);
-    }
-    if (arena_len) memcpy(pa, arena, arena_len);
-    return HostRunStaged(e, n, arena_len, verdict, rule, consumed, false);
+    HostCtx *H = nullptr;
+    DevIn dev;
+    hipError_t rc = HostStage(e, {arena, arena_len, off, len, conn, n}, &H, &dev);
+    if (rc == hipSuccess) rc = HostRunStaged(e, H, n, arena_len, verdict, rule, consumed, false);
+    return (int)rc;
 }
 
-// l7g_classify_host with the access-log outputs: the calling thread's stream
-// and staging, one copy in, the launch plan of Classify with the log outputs
-// (always launched: no resident service, no zero-copy), the outputs, records
-// and topic rows copied out, a wait.  The caller's topic rows go in first, so
-// that the rows no kernel writes (requests that are not Kafka) come back as
-// they were.
-int l7g_classify_logged_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
-                             const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule,
-                             uint32_t *consumed, const l7g_log_out_t *log) {
-    if (!log || !log->rec || (log->topic_stride && !log->topics)) return (int)hipErrorInvalidValue;
-    uint8_t *pa;
-    uint64_t *po;
-    uint32_t *pl, *pc;
-    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
-    if (rc0 != 0 || n == 0) return rc0;
-    memcpy(po, off, (size_t)n * 8);
-    memcpy(pl, len, (size_t)n * 4);
-    memcpy(pc, conn, (size_t)n * 4);
-    if (arena_len) memcpy(pa, arena, arena_len);
+// l7g_classify_host with the access-log outputs (the body of both logged
+// twins; all: l7g_classify_logged_all's plan, the text rows with it): the
+// calling thread's stream and staging, one copy in, the launch plan of
+// Classify with the log outputs (always launched: no resident service, no
+// zero-copy), the outputs and the log staging, laid out [records | span rows |
+// text rows], copied out, a wait.  The caller's span and text rows go in
+// first, so that what no kernel writes (rows of other protocols, bytes past a
+// row's written prefix) comes back as it was.
+static int ClassifyLoggedHost(l7g_engine *e, const DevIn &host, uint8_t *verdict, int32_t *rule, uint32_t *consumed,
+                              const l7g_log_all_out_t &log, bool all) {
     HostCtx *H = nullptr;
-    hipError_t rc = HostEnter(e, &H);
-    if (rc != hipSuccess) return (int)rc;
+    DevIn dev;
+    hipError_t rc = HostStage(e, host, &H, &dev);
+    const uint32_t n = host.n;
+    if (rc != hipSuccess || n == 0) return (int)rc;
     const size_t rec_b = (size_t)n * sizeof(l7g_logrec_t);
-    const size_t top_b = (size_t)n * log->topic_stride * sizeof(l7g_span_t);
-    if (rec_b + top_b > H->log_cap) {
-        hipStreamSynchronize(H->s);
-        if (H->log_dev) hipFree(H->log_dev);
-        if (H->log_pin) hipHostFree(H->log_pin);
-        H->log_dev = H->log_pin = nullptr;
-        H->log_cap = 0;
-        const size_t cap = rec_b + top_b + (rec_b + top_b) / 4;
-        if ((rc = hipMalloc(&H->log_dev, cap)) != hipSuccess) return (int)rc;
-        if ((rc = hipHostMalloc(&H->log_pin, cap, hipHostMallocDefault)) != hipSuccess) return (int)rc;
-        H->log_cap = cap;
+    const size_t span_b = (size_t)n * log.span_stride * sizeof(l7g_span_t);
+    const size_t text_b = (size_t)n * log.text_stride;
+    const size_t all_b = rec_b + span_b + text_b;
+    if ((rc = H->log.Grow(H->s, all_b)) != hipSuccess) return (int)rc;
+    uint8_t *d_log = H->log.dev, *p_log = H->log.pin, *d_out = H->dev + H->in_cap;
+    const LogOut lo{(LogRec *)d_log, span_b ? (LogSpan *)(d_log + rec_b) : nullptr, log.span_stride};
+    const LogText tx{text_b ? d_log + rec_b + span_b : nullptr, log.text_stride};
+    ClassifyOpts o;
+    o.host_conn = (const uint32_t *)(H->pin_in + CallConnOff(CallNn(n)));
+    o.log = &lo;
+    o.text = all ? &tx : nullptr;  // (Classify's plan differs on it)
+    rc = UploadStaged(H, dev);
+    if (rc == hipSuccess && span_b + text_b) {
+        if (span_b) memcpy(p_log + rec_b, log.spans, span_b);
+        if (text_b) memcpy(p_log + rec_b + span_b, log.text, text_b);
+        rc = hipMemcpyAsync(d_log + rec_b, p_log + rec_b, span_b + text_b, hipMemcpyHostToDevice, H->s);
     }
-    const size_t nn = CallNn(n);
-    uint8_t *d_in = H->dev, *d_out = H->dev + H->in_cap;
-    const LogOut lo{(LogRec *)H->log_dev, top_b ? (LogSpan *)(H->log_dev + rec_b) : nullptr, log->topic_stride};
-    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
-    if (rc == hipSuccess && top_b) {
-        memcpy(H->log_pin + rec_b, log->topics, top_b);
-        rc = hipMemcpyAsync(H->log_dev + rec_b, H->log_pin + rec_b, top_b, hipMemcpyHostToDevice, H->s);
-    }
-    if (rc == hipSuccess)
-        rc = (hipError_t)Classify(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
-                                  (const uint32_t *)(d_in + CallLenOff(nn)), (const uint32_t *)(d_in + CallConnOff(nn)),
-                                  n, d_out, (int32_t *)(d_out + CallRuleOff(n)), (uint32_t *)(d_out + CallConsumedOff(n)),
-                                  nullptr, H->s, pc, nullptr, nullptr, &lo);
+    if (rc == hipSuccess) rc = (hipError_t)Classify(e, dev, OutViews(d_out, n), H->s, o);
     if (rc == hipSuccess) rc = hipMemcpyAsync(H->pin_out, d_out, CallOutBytes(n), hipMemcpyDeviceToHost, H->s);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(H->log_pin, H->log_dev, rec_b + top_b, hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(p_log, d_log, all_b, hipMemcpyDeviceToHost, H->s);
     if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
     if (rc == hipSuccess) {
-        memcpy(verdict, H->pin_out, n);
-        memcpy(rule, H->pin_out + CallRuleOff(n), (size_t)n * 4);
-        memcpy(consumed, H->pin_out + CallConsumedOff(n), (size_t)n * 4);
-        memcpy(log->rec, H->log_pin, rec_b);
-        if (top_b) memcpy(log->topics, H->log_pin + rec_b, top_b);
+        UnpackOut(H, n, verdict, rule, consumed);
+        memcpy(log.rec, p_log, rec_b);
+        if (span_b) memcpy(log.spans, p_log + rec_b, span_b);
+        if (text_b) memcpy(log.text, p_log + rec_b + span_b, text_b);
     }
     return (int)rc;
 }
 
-// l7g_classify_logged_all with host buffers: l7g_classify_logged_host's
-// sequence over the same per-thread log staging, laid out [records | span rows
-// | text rows].  The caller's span and text rows go in first, so that what no
-// kernel writes (rows of other protocols, bytes past a row's written prefix)
-// comes back as it was.
+int l7g_classify_logged_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                             const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, int32_t *rule,
+                             uint32_t *consumed, const l7g_log_out_t *log) {
+    if (!log || !log->rec || (log->topic_stride && !log->topics)) return (int)hipErrorInvalidValue;
+    return ClassifyLoggedHost(e, {arena, arena_len, off, len, conn, n}, verdict, rule, consumed,
+                              {log->rec, log->topics, log->topic_stride, nullptr, 0}, false);
+}
+
 int l7g_classify_logged_all_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
                                  const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict,
                                  int32_t *rule, uint32_t *consumed, const l7g_log_all_out_t *log) {
     if (!log || !log->rec || (log->span_stride && !log->spans) || (log->text_stride && !log->text))
         return (int)hipErrorInvalidValue;
-    uint8_t *pa;
-    uint64_t *po;
-    uint32_t *pl, *pc;
-    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
-    if (rc0 != 0 || n == 0) return rc0;
-    memcpy(po, off, (size_t)n * 8);
-    memcpy(pl, len, (size_t)n * 4);
-    memcpy(pc, conn, (size_t)n * 4);
-    if (arena_len) memcpy(pa, arena, arena_len);
-    HostCtx *H = nullptr;
-    hipError_t rc = HostEnter(e, &H);
-    if (rc != hipSuccess) return (int)rc;
-    const size_t rec_b = (size_t)n * sizeof(l7g_logrec_t);
-    const size_t span_b = (size_t)n * log->span_stride * sizeof(l7g_span_t);
-    const size_t text_b = (size_t)n * log->text_stride;
-    const size_t all_b = rec_b + span_b + text_b;
-    if (all_b > H->log_cap) {
-        hipStreamSynchronize(H->s);
-        if (H->log_dev) hipFree(H->log_dev);
-        if (H->log_pin) hipHostFree(H->log_pin);
-        H->log_dev = H->log_pin = nullptr;
-        H->log_cap = 0;
-        const size_t cap = all_b + all_b / 4;
-        if ((rc = hipMalloc(&H->log_dev, cap)) != hipSuccess) return (int)rc;
-        if ((rc = hipHostMalloc(&H->log_pin, cap, hipHostMallocDefault)) != hipSuccess) return (int)rc;
-        H->log_cap = cap;
-    }
-    const size_t nn = CallNn(n);
-    uint8_t *d_in = H->dev, *d_out = H->dev + H->in_cap;
-    const LogOut lo{(LogRec *)H->log_dev, span_b ? (LogSpan *)(H->log_dev + rec_b) : nullptr, log->span_stride};
-    const LogText tx{text_b ? H->log_dev + rec_b + span_b : nullptr, log->text_stride};
-    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
-    if (rc == hipSuccess && span_b + text_b) {
-        if (span_b) memcpy(H->log_pin + rec_b, log->spans, span_b);
-        if (text_b) memcpy(H->log_pin + rec_b + span_b, log->text, text_b);
-        rc = hipMemcpyAsync(H->log_dev + rec_b, H->log_pin + rec_b, span_b + text_b, hipMemcpyHostToDevice, H->s);
-    }
-    if (rc == hipSuccess)
-        rc = (hipError_t)Classify(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
-                                  (const uint32_t *)(d_in + CallLenOff(nn)), (const uint32_t *)(d_in + CallConnOff(nn)),
-                                  n, d_out, (int32_t *)(d_out + CallRuleOff(n)), (uint32_t *)(d_out + CallConsumedOff(n)),
-                                  nullptr, H->s, pc, nullptr, nullptr, &lo, &tx);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(H->pin_out, d_out, CallOutBytes(n), hipMemcpyDeviceToHost, H->s);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(H->log_pin, H->log_dev, all_b, hipMemcpyDeviceToHost, H->s);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
-    if (rc == hipSuccess) {
-        memcpy(verdict, H->pin_out, n);
-        memcpy(rule, H->pin_out + CallRuleOff(n), (size_t)n * 4);
-        memcpy(consumed, H->pin_out + CallConsumedOff(n), (size_t)n * 4);
-        memcpy(log->rec, H->log_pin, rec_b);
-        if (span_b) memcpy(log->spans, H->log_pin + rec_b, span_b);
-        if (text_b) memcpy(log->text, H->log_pin + rec_b + span_b, text_b);
-    }
-    return (int)rc;
+    return ClassifyLoggedHost(e, {arena, arena_len, off, len, conn, n}, verdict, rule, consumed, *log, true);
 }
 
 // l7g_deny_replies with host buffers, over the calling thread's stream and
@@ -415,47 +367,22 @@ int l7g_deny_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_le
     if (e->device < 0) return (int)hipErrorNoDevice;
     if (!out || !out->off || !out->len || !out->total || (!out->buf && out->cap)) return (int)hipErrorInvalidValue;
     if (n && (!off || !len || !conn || !verdict)) return (int)hipErrorInvalidValue;
-    uint8_t *pa;
-    uint64_t *po;
-    uint32_t *pl, *pc;
-    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
-    if (rc0 != 0) return rc0;
-    if (n) {
-        memcpy(po, off, (size_t)n * 8);
-        memcpy(pl, len, (size_t)n * 4);
-        memcpy(pc, conn, (size_t)n * 4);
-    }
-    if (arena_len) memcpy(pa, arena, arena_len);
     HostCtx *H = nullptr;
-    hipError_t rc = HostEnter(e, &H);
+    DevIn dev;
+    hipError_t rc = HostStage(e, {arena, arena_len, off, len, conn, n}, &H, &dev);
     if (rc != hipSuccess) return (int)rc;
     const size_t o_off = ((size_t)n + 15) & ~(size_t)15, o_len = o_off + (size_t)n * 8;
     const size_t o_tot = (o_len + (size_t)n * 4 + 15) & ~(size_t)15, o_buf = o_tot + 16;
-    const size_t need = o_buf + out->cap;
-    if (need > H->reply_cap) {
-        hipStreamSynchronize(H->s);
-        if (H->reply_dev) hipFree(H->reply_dev);
-        if (H->reply_pin) hipHostFree(H->reply_pin);
-        H->reply_dev = H->reply_pin = nullptr;
-        H->reply_cap = 0;
-        const size_t cap = need + need / 4;
-        if ((rc = hipMalloc(&H->reply_dev, cap)) != hipSuccess) return (int)rc;
-        if ((rc = hipHostMalloc(&H->reply_pin, cap, hipHostMallocDefault)) != hipSuccess) return (int)rc;
-        H->reply_cap = cap;
-    }
-    const size_t nn = CallNn(n);
-    uint8_t *d_in = H->dev, *d_r = H->reply_dev, *p_r = H->reply_pin;
-    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
+    if ((rc = H->reply.Grow(H->s, o_buf + out->cap)) != hipSuccess) return (int)rc;
+    uint8_t *d_r = H->reply.dev, *p_r = H->reply.pin;
+    rc = UploadStaged(H, dev);
     if (rc == hipSuccess && n) {
         memcpy(p_r, verdict, n);
         rc = hipMemcpyAsync(d_r, p_r, n, hipMemcpyHostToDevice, H->s);
     }
     const l7g_reply_out_t dout{out->cap ? d_r + o_buf : nullptr, out->cap, (uint64_t *)(d_r + o_off),
                                (uint32_t *)(d_r + o_len), (uint64_t *)(d_r + o_tot)};
-    if (rc == hipSuccess)
-        rc = (hipError_t)DenyReplies(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
-                                     (const uint32_t *)(d_in + CallLenOff(nn)), (const uint32_t *)(d_in + CallConnOff(nn)),
-                                     n, d_r, &dout, H->s);
+    if (rc == hipSuccess) rc = (hipError_t)DenyReplies(e, dev, d_r, &dout, H->s);
     if (rc == hipSuccess)
         rc = hipMemcpyAsync(p_r + o_off, d_r + o_off, o_buf - o_off, hipMemcpyDeviceToHost, H->s);
     if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
@@ -487,56 +414,18 @@ int l7g_deny_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_le
 // staging: one copy in, the reply kernels, one copy out, a wait.
 int l7g_cass_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
                           const uint32_t *len, const uint32_t *conn, uint32_t n, uint8_t *verdict, uint32_t *consumed) {
-    uint8_t *pa;
-    uint64_t *po;
-    uint32_t *pl, *pc;
-    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
-    if (rc0 != 0) return rc0;
-    if (n) {
-        memcpy(po, off, (size_t)n * 8);
-        memcpy(pl, len, (size_t)n * 4);
-        memcpy(pc, conn, (size_t)n * 4);
-    }
-    if (arena_len) memcpy(pa, arena, arena_len);
     HostCtx *H = nullptr;
-    hipError_t rc = HostEnter(e, &H);
+    DevIn dev;
+    hipError_t rc = HostStage(e, {arena, arena_len, off, len, conn, n}, &H, &dev);
     if (rc != hipSuccess) return (int)rc;
-    const size_t nn = CallNn(n);
-    uint8_t *d_in = H->dev, *d_out = H->dev + H->in_cap;
-    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
-    if (rc == hipSuccess)
-        rc = (hipError_t)CassReplies(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
-                                     (const uint32_t *)(d_in + CallLenOff(nn)), (const uint32_t *)(d_in + CallConnOff(nn)),
-                                     n, d_out, (uint32_t *)(d_out + CallConsumedOff(n)), H->s);
+    uint8_t *d_out = H->dev + H->in_cap;
+    const DevOut o = OutViews(d_out, n);
+    rc = UploadStaged(H, dev);
+    if (rc == hipSuccess) rc = (hipError_t)CassReplies(e, dev, o.verdict, o.consumed, H->s);
     if (rc == hipSuccess && n) rc = hipMemcpyAsync(H->pin_out, d_out, CallOutBytes(n), hipMemcpyDeviceToHost, H->s);
     if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
-    if (rc == hipSuccess && n) {
-        memcpy(verdict, H->pin_out, n);
-        memcpy(consumed, H->pin_out + CallConsumedOff(n), (size_t)n * 4);
-    }
+    if (rc == hipSuccess && n) UnpackOut(H, n, verdict, nullptr, consumed);
     return (int)rc;
-}
-
-// The Kafka-session staging of the calling thread, grown to `need` bytes.
-static hipError_t KsessGrow(HostCtx *H, size_t need) {
-    if (need <= H->ksess_cap) return hipSuccess;
-    hipStreamSynchronize(H->s);
-    if (H->ksess_dev) hipFree(H->ksess_dev);
-    if (H->ksess_pin) hipHostFree(H->ksess_pin);
-    H->ksess_dev = H->ksess_pin = nullptr;
-    H->ksess_cap = 0;
-    const size_t cap = need + need / 4;
-    hipError_t rc = hipMalloc(&H->ksess_dev, cap);
-    if (rc == hipSuccess) rc = hipHostMalloc(&H->ksess_pin, cap, hipHostMallocDefault);
-    if (rc == hipSuccess) H->ksess_cap = cap;
-    return rc;
-}
-
-static void PutBE32(uint8_t *p, uint32_t v) {
-    p[0] = (uint8_t)(v >> 24);
-    p[1] = (uint8_t)(v >> 16);
-    p[2] = (uint8_t)(v >> 8);
-    p[3] = (uint8_t)v;
 }
 
 // l7g_kafka_forward with host buffers, over the calling thread's stream and
@@ -549,35 +438,22 @@ int l7g_kafka_forward_host(l7g_engine *e, uint8_t *arena, uint64_t arena_len, co
                            uint64_t now_ms, uint8_t *fwd, uint32_t *new_id) {
     if (e->device < 0) return (int)hipErrorNoDevice;
     if (n && (!off || !len || !conn || !verdict || !fwd || !new_id)) return (int)hipErrorInvalidValue;
-    uint8_t *pa;
-    uint64_t *po;
-    uint32_t *pl, *pc;
-    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
-    if (rc0 != 0) return rc0;
-    if (n) {
-        memcpy(po, off, (size_t)n * 8);
-        memcpy(pl, len, (size_t)n * 4);
-        memcpy(pc, conn, (size_t)n * 4);
-    }
-    if (arena_len) memcpy(pa, arena, arena_len);
     HostCtx *H = nullptr;
-    hipError_t rc = HostEnter(e, &H);
+    DevIn dev;
+    hipError_t rc = HostStage(e, {arena, arena_len, off, len, conn, n}, &H, &dev);
     if (rc != hipSuccess) return (int)rc;
     const size_t o_tag = ((size_t)n + 15) & ~(size_t)15, o_fwd = o_tag + (size_t)n * 8;
     const size_t o_id = (o_fwd + n + 15) & ~(size_t)15, end = o_id + (size_t)n * 4;
-    if ((rc = KsessGrow(H, end + 16)) != hipSuccess) return (int)rc;
-    const size_t nn = CallNn(n);
-    uint8_t *d_in = H->dev, *d_k = H->ksess_dev, *p_k = H->ksess_pin;
-    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
+    if ((rc = H->ksess.Grow(H->s, end + 16)) != hipSuccess) return (int)rc;
+    uint8_t *d_k = H->ksess.dev, *p_k = H->ksess.pin;
+    rc = UploadStaged(H, dev);
     if (rc == hipSuccess && n) {
         memcpy(p_k, verdict, n);
         if (tag) memcpy(p_k + o_tag, tag, (size_t)n * 8);
         rc = hipMemcpyAsync(d_k, p_k, o_fwd, hipMemcpyHostToDevice, H->s);
     }
     if (rc == hipSuccess)
-        rc = (hipError_t)l7g_kafka_forward(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
-                                           (const uint32_t *)(d_in + CallLenOff(nn)),
-                                           (const uint32_t *)(d_in + CallConnOff(nn)), d_k,
+        rc = (hipError_t)l7g_kafka_forward(e, (uint8_t *)dev.arena, arena_len, dev.off, dev.len, dev.conn, d_k,
                                            tag ? (const uint64_t *)(d_k + o_tag) : nullptr, n, now_ms, d_k + o_fwd,
                                            (uint32_t *)(d_k + o_id), H->s);
     if (rc == hipSuccess && n) rc = hipMemcpyAsync(p_k + o_fwd, d_k + o_fwd, end - o_fwd, hipMemcpyDeviceToHost, H->s);
@@ -600,31 +476,18 @@ int l7g_kafka_responses_host(l7g_engine *e, uint8_t *arena, uint64_t arena_len, 
     if (e->device < 0) return (int)hipErrorNoDevice;
     if (n && (!off || !len || !conn || !found || !orig_id || !api_key || !api_version || !tag))
         return (int)hipErrorInvalidValue;
-    uint8_t *pa;
-    uint64_t *po;
-    uint32_t *pl, *pc;
-    int rc0 = l7g_host_stage(e, n, arena_len, &pa, &po, &pl, &pc);
-    if (rc0 != 0) return rc0;
-    if (n) {
-        memcpy(po, off, (size_t)n * 8);
-        memcpy(pl, len, (size_t)n * 4);
-        memcpy(pc, conn, (size_t)n * 4);
-    }
-    if (arena_len) memcpy(pa, arena, arena_len);
     HostCtx *H = nullptr;
-    hipError_t rc = HostEnter(e, &H);
+    DevIn dev;
+    hipError_t rc = HostStage(e, {arena, arena_len, off, len, conn, n}, &H, &dev);
     if (rc != hipSuccess) return (int)rc;
     const size_t o_orig = (size_t)n * 8, o_key = o_orig + (size_t)n * 4, o_ver = o_key + (size_t)n * 2;
     const size_t o_found = o_ver + (size_t)n * 2, end = o_found + n;
-    if ((rc = KsessGrow(H, end + 16)) != hipSuccess) return (int)rc;
-    const size_t nn = CallNn(n);
-    uint8_t *d_in = H->dev, *d_k = H->ksess_dev, *p_k = H->ksess_pin;
-    rc = hipMemcpyAsync(d_in, H->pin_in, CallInBytes(nn, arena_len), hipMemcpyHostToDevice, H->s);
+    if ((rc = H->ksess.Grow(H->s, end + 16)) != hipSuccess) return (int)rc;
+    uint8_t *d_k = H->ksess.dev, *p_k = H->ksess.pin;
+    rc = UploadStaged(H, dev);
     if (rc == hipSuccess)
-        rc = (hipError_t)l7g_kafka_responses(e, d_in + CallArenaOff(nn), arena_len, (const uint64_t *)d_in,
-                                             (const uint32_t *)(d_in + CallLenOff(nn)),
-                                             (const uint32_t *)(d_in + CallConnOff(nn)), n, d_k + o_found,
-                                             (uint32_t *)(d_k + o_orig), (int16_t *)(d_k + o_key),
+        rc = (hipError_t)l7g_kafka_responses(e, (uint8_t *)dev.arena, arena_len, dev.off, dev.len, dev.conn, n,
+                                             d_k + o_found, (uint32_t *)(d_k + o_orig), (int16_t *)(d_k + o_key),
                                              (int16_t *)(d_k + o_ver), (uint64_t *)d_k, H->s);
     if (rc == hipSuccess && n) rc = hipMemcpyAsync(p_k, d_k, end, hipMemcpyDeviceToHost, H->s);
     if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);

@@ -2,43 +2,21 @@
 // tables (kernels/kafka_session.hip) and the calls over device pointers,
 // l7g_kafka_forward and l7g_kafka_responses, each on the caller's stream with
 // that stream's scratch.  Nothing of l7g_classify's plan is involved.  The
-// host-buffer twins are in host_call.cc.
-#include <algorithm>
-#include <cstring>
-
-#include "engine_state.h"
+// slot sync is sessions.h's, shared with cass_sessions.cc; the host-buffer
+// twins are in host_call.cc.
+#include "sessions.h"
 
 namespace {
-
-void set_err(char *err, size_t errlen, const char *m) {
-    if (err && errlen) {
-        strncpy(err, m, errlen - 1);
-        err[errlen - 1] = 0;
-    }
-}
-
-// Runs `f` (enqueues on the null stream) once no launched kernel can touch the
-// session tables, and waits for it.
-template <class F>
-hipError_t Quiet(l7g_engine *e, F f) {
-    hipError_t rc = WaitLastClassify(e);
-    if (rc == hipSuccess) rc = f();
-    if (rc == hipSuccess) rc = hipStreamSynchronize(nullptr);
-    return rc;
-}
 
 size_t TableBytes(const KafkaSessions &S) { return ((size_t)S.mask + 1) * sizeof(KafkaSessEntry); }
 constexpr size_t kStatBytes = (KSS_WORDS + 2) * sizeof(unsigned long long);
 
-// what every call over a batch starts with (e->mu held): the device, the
-// connection table, the slots and the pending resets
+// what every call here starts with (e->mu held): its checks, then CallBegin
+// with the Kafka sessions synced (the scratch follows the array checks)
 hipError_t Enter(l7g_engine *e) {
     if (e->device < 0) return hipErrorNoDevice;
     if (!e->ksess.tab) return hipErrorNotReady;
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = Upload(e);
-    if (rc == hipSuccess) rc = KafkaSessionsSync(e);
-    return rc;
+    return CallBegin(e, kSyncKafka, nullptr, nullptr);
 }
 
 }  // namespace
@@ -55,46 +33,10 @@ void KafkaSessionsFree(l7g_engine *e) {
 hipError_t KafkaSessionsSync(l7g_engine *e) {
     KafkaSessions &S = e->ksess;
     if (!S.tab) return hipSuccess;
-    hipError_t rc = hipSuccess;
-    const size_t need = std::max<size_t>(e->conns.size(), 1);
-    if (need > S.nslots) {  // grown with the connection table, the sessions so far kept
-        const size_t cap = std::max(need, (size_t)S.nslots * 2);
-        KafkaSessSlot *d = nullptr;
-        if ((rc = hipMalloc(&d, cap * sizeof(KafkaSessSlot))) != hipSuccess) return rc;
-        rc = Quiet(e, [&] {
-            hipError_t r = hipMemsetAsync(d, 0, cap * sizeof(KafkaSessSlot), nullptr);
-            if (r == hipSuccess && S.nslots)
-                r = hipMemcpyAsync(d, S.slots, (size_t)S.nslots * sizeof(KafkaSessSlot), hipMemcpyDeviceToDevice, nullptr);
-            return r;
-        });
-        if (rc != hipSuccess) { hipFree(d); return rc; }
-        if (S.slots) hipFree(S.slots);
-        S.slots = d;
-        S.nslots = (uint32_t)cap;
-    }
-    if (e->ksess_reset_all) {
-        // every session: zeroed slots and a zeroed table are the state sessions start in
-        rc = Quiet(e, [&] {
-            hipError_t r = hipMemsetAsync(S.slots, 0, (size_t)S.nslots * sizeof(KafkaSessSlot), nullptr);
-            if (r == hipSuccess) r = hipMemsetAsync(S.tab, 0, TableBytes(S), nullptr);
-            return r;
-        });
-    } else if (!e->ksess_reset.empty()) {
-        uint32_t *d = nullptr;
-        const size_t bytes = e->ksess_reset.size() * sizeof(uint32_t);
-        if ((rc = hipMalloc(&d, bytes)) != hipSuccess) return rc;
-        rc = Quiet(e, [&] {
-            hipError_t r = hipMemcpyAsync(d, e->ksess_reset.data(), bytes, hipMemcpyHostToDevice, nullptr);
-            if (r == hipSuccess) r = LaunchKafkaSessReset(S, d, (uint32_t)e->ksess_reset.size(), nullptr);
-            return r;
-        });
-        hipFree(d);
-    }
-    if (rc == hipSuccess) {
-        e->ksess_reset.clear();
-        e->ksess_reset_all = false;
-    }
-    return rc;
+    return SlotsSync(
+        e, S.slots, S.nslots, e->ksess_reset, e->ksess_reset_all,
+        [&] { return hipMemsetAsync(S.tab, 0, TableBytes(S), nullptr); },
+        [&](const uint32_t *conn, uint32_t n) { return LaunchKafkaSessReset(S, conn, n, nullptr); });
 }
 
 extern "C" {
@@ -144,9 +86,7 @@ int l7g_kafka_forward(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const u
     if ((rc = S->Grow(&S->d_ksess, &S->ksess_cap, need, need)) != hipSuccess) return (int)rc;
     const KafkaSessBatch B{arena, arena_len, off, len, conn, e->d_conns, n, nconns};
     rc = LaunchKafkaSessForward(B, e->ksess, verdict, tag, now_ms, fwd, new_id, S->d_ksess, S->ksess_cap, s);
-    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
-    if (rc == hipSuccess) S->launched = true;
-    return (int)rc;
+    return (int)CallEnd(S, s, rc);
 }
 
 int l7g_kafka_responses(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
@@ -163,9 +103,7 @@ int l7g_kafka_responses(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const
     if ((rc = S->Grow(&S->d_ksess, &S->ksess_cap, need, need)) != hipSuccess) return (int)rc;
     const KafkaSessBatch B{arena, arena_len, off, len, conn, e->d_conns, n, (uint32_t)e->conns.size()};
     rc = LaunchKafkaSessResponses(B, e->ksess, found, orig_id, api_key, api_version, tag, S->d_ksess, S->ksess_cap, s);
-    if (rc == hipSuccess) rc = hipEventRecord(S->done_ev, s);
-    if (rc == hipSuccess) S->launched = true;
-    return (int)rc;
+    return (int)CallEnd(S, s, rc);
 }
 
 int l7g_kafka_session_gc(l7g_engine *e, uint64_t now_ms, uint64_t lifetime_ms, uint64_t *expired) {
