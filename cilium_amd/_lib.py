@@ -50,6 +50,8 @@ EXPORTS = (
     "l7g_classify_logged_all", "l7g_classify_logged_all_host", "l7g_cass_action_name",
     "l7g_kafka_sessions_enable", "l7g_kafka_forward", "l7g_kafka_responses", "l7g_kafka_forward_host",
     "l7g_kafka_responses_host", "l7g_kafka_session_gc", "l7g_kafka_session_reset", "l7g_kafka_session_stats",
+    "l7g_mc_sessions_enable", "l7g_mc_forward", "l7g_mc_replies", "l7g_mc_forward_host", "l7g_mc_replies_host",
+    "l7g_mc_session_reset", "l7g_mc_session_stats", "l7g_mc_denied_message",
 )
 
 
@@ -226,6 +228,19 @@ def load(path=None):
         lib.l7g_kafka_session_reset.argtypes = [vp, vp, u32]
         lib.l7g_kafka_session_stats.argtypes = [vp, C.POINTER(u64)]
         lib.l7g_kafka_session_stats.restype = None
+    # (the same for the memcached sessions: tests/test_mc_sessions_host.py)
+    if hasattr(lib, "l7g_mc_sessions_enable"):
+        u64, u32 = C.c_uint64, C.c_uint32
+        lib.l7g_mc_sessions_enable.argtypes = [vp, u32, cp, sz]
+        lib.l7g_mc_forward.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, u32, vp, vp]
+        lib.l7g_mc_replies.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+        lib.l7g_mc_forward_host.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, u32, vp]
+        lib.l7g_mc_replies_host.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
+        lib.l7g_mc_session_reset.argtypes = [vp, vp, u32]
+        lib.l7g_mc_session_stats.argtypes = [vp, C.POINTER(u64)]
+        lib.l7g_mc_session_stats.restype = None
+        lib.l7g_mc_denied_message.restype = vp
+        lib.l7g_mc_denied_message.argtypes = [C.c_int, C.POINTER(C.c_size_t)]
     _libs[path] = lib
     return lib
 
@@ -267,6 +282,19 @@ def deny_reply_template(proto):
     n = C.c_size_t(0)
     p = load().l7g_deny_reply_template(int(proto), C.byref(n))
     return C.string_at(p, n.value) if p else b""
+
+
+# bytes a wave of the memcached sessions' reply kernel looks at per step (csrc/kernels/mc_session.h kMcSessStep)
+MC_SESS_WINDOW = 64
+
+
+def mc_denied_message(binary=False):
+    """The memcached parsers' denied message (csrc/deny_templates.h): the text
+    parser's 28 bytes, or the binary parser's 37 (the sender sets byte 0 =
+    0x81 | the request's byte 0)."""
+    n = C.c_size_t(0)
+    p = load().l7g_mc_denied_message(1 if binary else 0, C.byref(n))
+    return C.string_at(p, n.value)
 
 
 def kafka_deny_response(req):

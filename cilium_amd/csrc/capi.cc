@@ -1,8 +1,8 @@
 // C-ABI implementation (include/l7gpu.h): engine lifetime, policy versions,
 // compiled tables across ranks, the connection table and its upload, and the
 // statistics, profile and debug exports (product code).  The launch plan is
-// classify.cc, the session tables cass_sessions.cc and kafka_sessions.cc, the
-// host-buffer calls host_call.cc, the resident services service.cc;
+// classify.cc, the session tables cass_sessions.cc, kafka_sessions.cc and
+// mc_sessions.cc, the host-buffer calls host_call.cc, the resident services service.cc;
 // engine_state.h holds what they share.
 #include <algorithm>
 #include <cstring>
@@ -316,6 +316,7 @@ void l7g_engine_destroy(l7g_engine *e) {
     if (e->d_flow) hipFree(e->d_flow);
     SessionsFree(e);
     KafkaSessionsFree(e);
+    McSessionsFree(e);
     if (e->d_zreg) hipFree(e->d_zreg);
     if (e->zreg_ev) hipEventDestroy(e->zreg_ev);
     for (hipEvent_t ev : e->prof_ev)
@@ -425,6 +426,8 @@ int l7g_conns_set(l7g_engine *e, const l7g_conn_t *conns, uint32_t n, char *err,
     e->sess_reset.clear();
     e->ksess_reset_all = e->ksess.tab != nullptr;
     e->ksess_reset.clear();
+    e->mcsess_reset_all = e->mcsess.stats != nullptr;
+    e->mcsess_reset.clear();
     return 0;
 }
 
@@ -456,6 +459,7 @@ int l7g_conn_update(l7g_engine *e, uint32_t index, const l7g_conn_t *conn, char 
     // the new-connection event: proxylib makes a new parser there
     if (e->sess.by_id && !e->sess_reset_all) e->sess_reset.push_back(index);
     if (e->ksess.tab && !e->ksess_reset_all) e->ksess_reset.push_back(index);
+    if (e->mcsess.stats && !e->mcsess_reset_all) e->mcsess_reset.push_back(index);
     return 0;
 }
 

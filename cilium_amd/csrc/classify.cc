@@ -65,6 +65,7 @@ hipError_t CallBegin(l7g_engine *e, unsigned sync, hipStream_t s, StreamScratch 
     if (rc == hipSuccess) rc = Upload(e);
     if (rc == hipSuccess && (sync & kSyncCass)) rc = SessionsSync(e);
     if (rc == hipSuccess && (sync & kSyncKafka)) rc = KafkaSessionsSync(e);
+    if (rc == hipSuccess && (sync & kSyncMc)) rc = McSessionsSync(e);
     if (rc == hipSuccess && scratch) rc = GetScratch(e, s, scratch);
     return rc;
 }

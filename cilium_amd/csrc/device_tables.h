@@ -551,6 +551,71 @@ struct KafkaSessBatch {
     uint32_t n, nconns;
 };
 
+// Memcached sessions (l7g_mc_sessions_enable; kernels/memcached_session.hip):
+// what proxylib's two memcached parsers keep per connection, resident in HBM.
+// One slot per connection index; zeroed = a new connection.
+//   text (text/parser.go): replyQueue is a ring of McSessIntent, `cap` entries
+//   per connection at ring[connection * cap], the oldest at head, count queued.
+//   binary (binary/parser.go): requestCount, replyCount, and injectQueue
+//   reduced to its head: nothing queued yet (MCB_EMPTY), a head
+//   that fires when replies + 1 reaches armed_id (MCB_ARMED), or a head that
+//   can no longer fire (MCB_BLOCKED), behind which nothing is ever reached.
+enum : uint8_t { MCK_NONE = 0, MCK_TEXT = 1, MCK_BINARY = 2 };       // McSessSlot::kind, as DevConn::flags & 3
+enum : uint8_t { MCB_EMPTY = 0, MCB_ARMED = 1, MCB_BLOCKED = 2 };    // McSessSlot::bstate
+// How a text command's reply is framed (text/parser.go:218-261)
+enum : uint8_t { MCC_OTHER = 0, MCC_LINE = 1, MCC_END = 2, MCC_CRAWLER = 3 };
+constexpr uint32_t kMcDeniedTextLen = 28, kMcDeniedBinaryLen = 37;  // the denied messages (deny_templates.h)
+struct McSessSlot {  // 32 B
+    uint32_t head, count;         // text: the ring
+    uint32_t requests, replies;   // binary: requestCount, replyCount (uint32 arithmetic, as the reference's)
+    uint32_t armed_id;            // binary, MCB_ARMED: injectQueue[0].requestID
+    uint8_t kind;                 // MCK_*: the parser the first participating request locked
+    uint8_t watching;             // text: a watch request was seen
+    uint8_t bstate;               // MCB_*
+    uint8_t armed_magic;          // binary, MCB_ARMED: injectQueue[0].magic
+    uint32_t pad[2];
+};
+static_assert(sizeof(McSessSlot) == 32, "McSessSlot layout");
+struct McSessIntent {  // 16 B
+    uint64_t tag;      // the caller's handle
+    uint8_t cls;       // MCC_*
+    uint8_t denied;
+    uint8_t pad[6];
+};
+static_assert(sizeof(McSessIntent) == 16, "McSessIntent layout");
+enum : int {
+    MSS_FULL = 0, MSS_MISMATCH = 1, MSS_INJECT_NOW = 2, MSS_INJECT_QUEUED = 3, MSS_PASSED = 4, MSS_ERRORS = 5,
+    MSS_WORDS = 6
+};
+struct McSessions {
+    McSessSlot *slots;       // null: sessions are off
+    uint32_t nslots;
+    uint32_t cap;            // ring entries per connection (a power of two)
+    McSessIntent *ring;      // nslots * cap
+    unsigned long long *stats;  // MSS_*, then two words of the live count
+};
+// One l7g_mc_forward / l7g_mc_replies call as its kernels see it: request (or
+// stream) i is arena[offs[i] .. offs[i] + lens[i]) on connection conn_ids[i].
+struct McSessBatch {
+    const uint8_t *arena;
+    uint64_t arena_len;
+    const uint64_t *offs;
+    const uint32_t *lens;
+    const uint32_t *conn_ids;
+    const DevConn *conns;
+    uint32_t n, nconns;
+};
+// l7g_mc_replies' outputs (op_aux may be null)
+struct McReplyOut {
+    uint8_t *op_kind;
+    uint32_t *op_n;
+    uint64_t *op_aux;
+    uint32_t *nops;
+    uint8_t *result;
+    uint64_t *taken;
+    uint32_t max_ops;
+};
+
 #if defined(__HIPCC__)
 // A lane's large-NFA scratch (2 W words), by its index in the launch
 __device__ __forceinline__ uint64_t *l7_nfa_lane_scratch(uint64_t *base, uint32_t words) {

@@ -2,8 +2,8 @@
 // its launch plan, and the few internals shared by capi.cc (lifetime, policy,
 // tables, connections, statistics), classify.cc (the launch plan and the call
 // frame of every device-pointer entry: DevIn, DevOut, CallBegin, CallEnd),
-// cass_sessions.cc and kafka_sessions.cc (the session tables; their shared
-// lifetime is sessions.h), host_call.cc (the per-thread host staging path:
+// cass_sessions.cc, kafka_sessions.cc and mc_sessions.cc (the session tables;
+// their shared lifetime is sessions.h), host_call.cc (the per-thread host staging path:
 // HostCtx, StagePair, CallViews) and service.cc (the resident services).
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -67,6 +67,10 @@ struct StreamScratch {
     // l7g_kafka_responses: the entry each response found (bytes, grow-only)
     void *d_ksess = nullptr;
     size_t ksess_cap = 0;
+    // l7g_mc_forward: [keys | sorted keys | info bytes | scan elements | scanned | per-connection segments |
+    // sort / scan temporary storage] (bytes, grow-only)
+    void *d_mcsess = nullptr;
+    size_t mcsess_cap = 0;
     // completion of the last call's kernels on this stream
     hipEvent_t done_ev = nullptr;
     bool launched = false;
@@ -97,7 +101,7 @@ struct StreamScratch {
         if (join_ev) hipEventDestroy(join_ev);
         if (side) hipStreamDestroy(side);
         for (void *p : {(void *)d_bignfa, (void *)d_grp, (void *)d_sel, (void *)d_nfa, (void *)d_hist, d_use, (void *)d_work,
-                        d_reply, d_ksess})
+                        d_reply, d_ksess, d_mcsess})
             if (p) hipFree(p);
         if (done_ev) hipEventDestroy(done_ev);
     }
@@ -172,7 +176,9 @@ struct HostCtx {
     // l7g_kafka_forward_host / l7g_kafka_responses_host: what the call layout has no place for (the verdicts
     // and tags in, the per-frame outputs back)
     StagePair ksess;
-    ~HostCtx() {  // (the three pairs free themselves after this, the stream idle by then)
+    // l7g_mc_forward_host / l7g_mc_replies_host: likewise (the verdicts and tags in, act back; the ops back)
+    StagePair mcsess;
+    ~HostCtx() {  // (the four pairs free themselves after this, the stream idle by then)
         if (s) hipStreamSynchronize(s);
         if (dev) hipFree(dev);
         if (pin_in) hipHostFree(pin_in);
@@ -326,6 +332,12 @@ struct l7g_engine {
     std::vector<uint32_t> ksess_reset;
     bool ksess_reset_all = false;
     uint64_t ksess_expired = 0;  // entries l7g_kafka_session_gc dropped since enable
+    // memcached sessions (l7g_mc_sessions_enable; on while mcsess.stats is set), kept as the other two: one slot
+    // per connection index and its ring beside it (kernels/memcached_session.hip), the pending resets
+    McSessions mcsess{};
+    uint32_t mcsess_ring_slots = 0;  // connections the ring has room for (follows mcsess.nslots)
+    std::vector<uint32_t> mcsess_reset;
+    bool mcsess_reset_all = false;
     // Every stream's last completion event (StreamScratch::done_ev) is waited
     // on -- never a caller's stream, which may be gone by then -- before the
     // engine rewrites or frees anything a launched kernel reads: the
@@ -395,12 +407,15 @@ void SessionsFree(l7g_engine *e);
 // kafka_sessions.cc (e->mu held): the same for the Kafka sessions
 hipError_t KafkaSessionsSync(l7g_engine *e);
 void KafkaSessionsFree(l7g_engine *e);
+// mc_sessions.cc (e->mu held): the same for the memcached sessions
+hipError_t McSessionsSync(l7g_engine *e);
+void McSessionsFree(l7g_engine *e);
 // classify.cc (e->mu held): the scratch of stream s, the call ordered behind that scratch's last user
 hipError_t GetScratch(l7g_engine *e, hipStream_t s, StreamScratch **out);
 // classify.cc (e->mu held, the entry's own checks passed): what every call over a batch starts with -- the
 // device, the tables and connections uploaded, the named sessions synced, and (scratch not null) GetScratch --
 // and ends with: done_ev recorded behind the call's launches, which WaitLastClassify waits on.
-enum : unsigned { kSyncNone = 0, kSyncCass = 1, kSyncKafka = 2 };
+enum : unsigned { kSyncNone = 0, kSyncCass = 1, kSyncKafka = 2, kSyncMc = 4 };
 hipError_t CallBegin(l7g_engine *e, unsigned sync, hipStream_t s, StreamScratch **scratch);
 hipError_t CallEnd(StreamScratch *S, hipStream_t s, hipError_t rc);
 // classify.cc: l7g_classify and its logged forms (device pointers; takes e->mu)

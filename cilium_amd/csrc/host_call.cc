@@ -502,4 +502,71 @@ int l7g_kafka_responses_host(l7g_engine *e, uint8_t *arena, uint64_t arena_len, 
     return 0;
 }
 
+// l7g_mc_forward with host buffers, over the calling thread's stream and
+// staging: the inputs, the verdicts and the tags copied in, the forward
+// kernels, act copied out and waited for.  The session staging is
+// [verdict | tag | act].
+int l7g_mc_forward_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                        const uint32_t *len, const uint32_t *conn, const uint8_t *verdict, const uint64_t *tag,
+                        uint32_t n, uint8_t *act) {
+    if (e->device < 0) return (int)hipErrorNoDevice;
+    if (n && (!off || !len || !conn || !verdict || !act)) return (int)hipErrorInvalidValue;
+    HostCtx *H = nullptr;
+    DevIn dev;
+    hipError_t rc = HostStage(e, {arena, arena_len, off, len, conn, n}, &H, &dev);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t o_tag = ((size_t)n + 15) & ~(size_t)15, o_act = o_tag + (size_t)n * 8, end = o_act + n;
+    if ((rc = H->mcsess.Grow(H->s, end + 16)) != hipSuccess) return (int)rc;
+    uint8_t *d_m = H->mcsess.dev, *p_m = H->mcsess.pin;
+    rc = UploadStaged(H, dev);
+    if (rc == hipSuccess && n) {
+        memcpy(p_m, verdict, n);
+        if (tag) memcpy(p_m + o_tag, tag, (size_t)n * 8);
+        rc = hipMemcpyAsync(d_m, p_m, o_act, hipMemcpyHostToDevice, H->s);
+    }
+    if (rc == hipSuccess)
+        rc = (hipError_t)l7g_mc_forward(e, dev.arena, arena_len, dev.off, dev.len, dev.conn, d_m,
+                                        tag ? (const uint64_t *)(d_m + o_tag) : nullptr, n, d_m + o_act, H->s);
+    if (rc == hipSuccess && n) rc = hipMemcpyAsync(p_m + o_act, d_m + o_act, n, hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
+    if (rc == hipSuccess && n) memcpy(act, p_m + o_act, n);
+    return (int)rc;
+}
+
+// l7g_mc_replies with host buffers, likewise: the streams copied in, the reply
+// kernel, the outputs copied out ([taken | op_aux | op_n | nops | op_kind |
+// result] in the session staging).
+int l7g_mc_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *s_off,
+                        const uint32_t *s_len, const uint32_t *s_conn, uint32_t n, uint32_t max_ops, uint8_t *op_kind,
+                        uint32_t *op_n, uint64_t *op_aux, uint32_t *nops, uint8_t *result, uint64_t *taken) {
+    if (e->device < 0) return (int)hipErrorNoDevice;
+    if (n && (!s_off || !s_len || !s_conn || !nops || !result || !taken || (max_ops && (!op_kind || !op_n))))
+        return (int)hipErrorInvalidValue;
+    HostCtx *H = nullptr;
+    DevIn dev;
+    hipError_t rc = HostStage(e, {arena, arena_len, s_off, s_len, s_conn, n}, &H, &dev);
+    if (rc != hipSuccess) return (int)rc;
+    const size_t slots = (size_t)n * max_ops;
+    const size_t o_aux = (size_t)n * 8, o_n = o_aux + slots * 8, o_nops = o_n + slots * 4, o_kind = o_nops + (size_t)n * 4;
+    const size_t o_res = o_kind + slots, end = o_res + n;
+    if ((rc = H->mcsess.Grow(H->s, end + 16)) != hipSuccess) return (int)rc;
+    uint8_t *d_m = H->mcsess.dev, *p_m = H->mcsess.pin;
+    rc = UploadStaged(H, dev);
+    if (rc == hipSuccess && n) rc = hipMemsetAsync(d_m, 0, end, H->s);  // (op slots past nops come back as zeros)
+    if (rc == hipSuccess)
+        rc = (hipError_t)l7g_mc_replies(e, dev.arena, arena_len, dev.off, dev.len, dev.conn, n, max_ops, d_m + o_kind,
+                                        (uint32_t *)(d_m + o_n), (uint64_t *)(d_m + o_aux), (uint32_t *)(d_m + o_nops),
+                                        d_m + o_res, (uint64_t *)d_m, H->s);
+    if (rc == hipSuccess && n) rc = hipMemcpyAsync(p_m, d_m, end, hipMemcpyDeviceToHost, H->s);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(H->s);
+    if (rc != hipSuccess || n == 0) return (int)rc;
+    memcpy(taken, p_m, (size_t)n * 8);
+    if (op_aux) memcpy(op_aux, p_m + o_aux, slots * 8);
+    if (slots) memcpy(op_n, p_m + o_n, slots * 4);
+    memcpy(nops, p_m + o_nops, (size_t)n * 4);
+    if (slots) memcpy(op_kind, p_m + o_kind, slots);
+    memcpy(result, p_m + o_res, n);
+    return 0;
+}
+
 }  // extern "C"

@@ -73,6 +73,14 @@ hipError_t LaunchKafkaSessGc(const KafkaSessions &S, uint64_t now_ms, uint64_t l
                              hipStream_t stream);
 hipError_t LaunchKafkaSessReset(const KafkaSessions &S, const uint32_t *conn, uint32_t n, hipStream_t stream);
 hipError_t LaunchKafkaSessLive(const KafkaSessions &S, unsigned long long *out2, hipStream_t stream);
+// memcached sessions (kernels/memcached_session.hip): l7g_mc_forward, l7g_mc_replies and the slots' upkeep;
+// scratch: McSessForwardScratchBytes of the call (0: the batch is too large), 256-byte aligned
+size_t McSessForwardScratchBytes(uint32_t n, uint32_t nconns);
+hipError_t LaunchMcSessForward(const McSessBatch &B, const McSessions &S, const uint8_t *verdict, const uint64_t *tag,
+                               uint8_t *act, void *scratch, size_t scratch_bytes, hipStream_t stream);
+hipError_t LaunchMcSessReplies(const McSessBatch &B, const McSessions &S, const McReplyOut &O, hipStream_t stream);
+hipError_t LaunchMcSessReset(const McSessions &S, const uint32_t *conn, uint32_t n, hipStream_t stream);
+hipError_t LaunchMcSessLive(const McSessions &S, unsigned long long *out2, hipStream_t stream);
 hipError_t LaunchCounters(const uint8_t *verdict, const int32_t *rule, uint32_t n, uint32_t nrules,
                           uint64_t *counters, uint32_t *scratch, hipStream_t stream);
 size_t CountersScratchBytes();

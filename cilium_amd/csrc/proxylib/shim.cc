@@ -181,13 +181,13 @@ long FindCRLF(const std::string &d, size_t from = 0) {
     return p == std::string::npos ? -1 : (long)p;
 }
 
-const char kDeniedText[] = "CLIENT_ERROR access denied\r\n";  // text/parser.go:327
-// (the HTTP 403, the cassandra unauthorized frame and r2d2's error line: deny_templates.h)
+// (the denied messages -- memcached's two, the HTTP 403, the cassandra unauthorized frame and r2d2's
+// error line: deny_templates.h)
 using l7::kCassUnauth;
 using l7::kDenied403;
 using l7::kR2Error;
-const uint8_t kDeniedBinary[37] = {0x81, 0, 0, 0, 0, 0, 0, 8, 0, 0, 0, 0x0d, 0, 0, 0, 0, 0, 0, 0,
-                                   0,    0, 0, 0, 0, 'a', 'c', 'c', 'e', 's', 's', ' ', 'd', 'e', 'n', 'i', 'e', 'd'};
+const auto &kDeniedText = l7::kMcDeniedText;
+const auto &kDeniedBinary = l7::kMcDeniedBinary;
 
 }  // namespace
 namespace l7 {

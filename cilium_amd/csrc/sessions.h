@@ -1,5 +1,5 @@
-// What the session tables of both protocols share (cass_sessions.cc,
-// kafka_sessions.cc): one slot per connection index, grown with the connection
+// What the session tables of the three protocols share (cass_sessions.cc,
+// kafka_sessions.cc, mc_sessions.cc): one slot per connection index, grown with the connection
 // table, and the new-connection events applied before the next launch.
 #pragma once
 #include "engine_state.h"

@@ -427,6 +427,86 @@ class Engine:
         self._lib.l7g_kafka_session_stats(self._h, out)
         return dict(zip(self.KAFKA_SESSION_STATS, [int(x) for x in out]))
 
+    # ----------------------------------------------------- memcached sessions
+    def mc_sessions(self, max_pending):
+        """Device-resident memcached reply queues (l7g_mc_sessions_enable): with
+        max_pending > 0 the engine keeps each connection's text reply queue (a
+        ring of that capacity, rounded up to a power of two) and binary
+        counters; 0 turns that off."""
+        err = C.create_string_buffer(512)
+        rc = self._lib.l7g_mc_sessions_enable(self._h, int(max_pending), err, 512)
+        if rc != 0:
+            raise RuntimeError(f"l7g_mc_sessions_enable: HIP error {rc}: " + err.value.decode(errors="replace"))
+
+    def mc_forward(self, arena, offsets, lengths, conn_ids, verdict, tags=None):
+        """The request direction over a batch (host buffers), after classify
+        with its verdicts; returns act (l7gpu.h has the codes)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        v = np.ascontiguousarray(verdict, dtype=np.uint8)
+        tg = None if tags is None else np.ascontiguousarray(tags, dtype=np.uint64)
+        n = len(off)
+        act = np.zeros(n, np.uint8)
+        rc = self._lib.l7g_mc_forward_host(self._h, arena.ctypes.data, arena.nbytes, off.ctypes.data, ln.ctypes.data,
+                                           cid.ctypes.data, v.ctypes.data, None if tg is None else tg.ctypes.data, n,
+                                           act.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"l7g_mc_forward_host failed: HIP error {rc}")
+        return act
+
+    def mc_forward_device(self, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, verdict_ptr, tag_ptr, n, act_ptr,
+                          stream=0):
+        """l7g_mc_forward: all pointers are device addresses (tag_ptr may be 0)."""
+        rc = self._lib.l7g_mc_forward(self._h, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, verdict_ptr,
+                                      tag_ptr or None, n, act_ptr, stream or None)
+        if rc != 0:
+            raise RuntimeError(f"l7g_mc_forward failed: HIP error {rc}")
+
+    def mc_replies(self, arena, offsets, lengths, conn_ids, max_ops=16):
+        """The reply direction over a batch of streams (host buffers): returns
+        (op_kind[n, max_ops], op_n, op_aux, nops[n], result[n], taken[n])."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        n = len(off)
+        kind = np.zeros((n, max_ops), np.uint8)
+        opn = np.zeros((n, max_ops), np.uint32)
+        aux = np.zeros((n, max_ops), np.uint64)
+        nops = np.zeros(n, np.uint32)
+        res = np.zeros(n, np.uint8)
+        taken = np.zeros(n, np.uint64)
+        rc = self._lib.l7g_mc_replies_host(self._h, arena.ctypes.data, arena.nbytes, off.ctypes.data, ln.ctypes.data,
+                                           cid.ctypes.data, n, int(max_ops), kind.ctypes.data, opn.ctypes.data,
+                                           aux.ctypes.data, nops.ctypes.data, res.ctypes.data, taken.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"l7g_mc_replies_host failed: HIP error {rc}")
+        return kind, opn, aux, nops, res, taken
+
+    def mc_replies_device(self, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, max_ops, op_kind_ptr, op_n_ptr,
+                          op_aux_ptr, nops_ptr, result_ptr, taken_ptr, stream=0):
+        """l7g_mc_replies: all pointers are device addresses (op_aux_ptr may be 0)."""
+        rc = self._lib.l7g_mc_replies(self._h, arena_ptr, arena_len, off_ptr, len_ptr, conn_ptr, n, int(max_ops),
+                                      op_kind_ptr, op_n_ptr, op_aux_ptr or None, nops_ptr, result_ptr, taken_ptr,
+                                      stream or None)
+        if rc != 0:
+            raise RuntimeError(f"l7g_mc_replies failed: HIP error {rc}")
+
+    def mc_session_reset(self, conn_ids):
+        cid = np.ascontiguousarray(conn_ids, dtype=np.uint32)
+        rc = self._lib.l7g_mc_session_reset(self._h, cid.ctypes.data, len(cid))
+        if rc != 0:
+            raise RuntimeError(f"l7g_mc_session_reset failed: HIP error {rc}")
+
+    MC_SESSION_STATS = ("queued", "sessions", "full", "mismatch", "inject_now", "inject_queued", "passed", "errors")
+
+    def mc_session_stats(self):
+        out = (C.c_uint64 * 8)()
+        self._lib.l7g_mc_session_stats(self._h, out)
+        return dict(zip(self.MC_SESSION_STATS, [int(x) for x in out]))
+
     def conn_update(self, index, conn):
         """One connection set (or added) alone: l7g_conn_update, the new-connection event."""
         arr = conns_array([conn])

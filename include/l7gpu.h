@@ -34,6 +34,10 @@
  *                       Envoy's 403 local reply                    envoy/cilium_l7policy.cc:90-96,171-177,
  *                       the cassandra / r2d2 parsers' injected errors
  *                                                                  proxylib/cassandra/cassandraparser.go:269-278
+ *   l7g_mc_forward,     the memcached parsers' reply bookkeeping: the text reply queue,
+ *   l7g_mc_replies      the binary inject queue, reply framing        proxylib/memcached/text/parser.go:173-331,
+ *                                                                  proxylib/memcached/binary/parser.go:58-165,
+ *                       under the connection's op loop             proxylib/proxylib/connection.go:118-174
  *   counters argument   Endpoint.UpdateProxyStatistics counters    pkg/endpoint/endpoint.go:2207-2233
  *   of l7g_classify     (per-rule allow hits + per-verdict totals, accumulated on the device)
  *
@@ -594,6 +598,132 @@ int l7g_kafka_responses_host(l7g_engine *e, uint8_t *arena, uint64_t arena_len, 
 int l7g_kafka_session_gc(l7g_engine *e, uint64_t now_ms, uint64_t lifetime_ms, uint64_t *expired);
 int l7g_kafka_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n);
 void l7g_kafka_session_stats(l7g_engine *e, uint64_t out[7]);
+
+/* Memcached sessions (off by default): the reply queue of the text parser
+ * (proxylib/memcached/text/parser.go) and the request / reply counters and
+ * inject queue of the binary parser (proxylib/memcached/binary/parser.go) for
+ * device-resident batches, one session per connection index.  A post-pass:
+ * l7g_classify and its kernels are not involved.  The proxylib shim stays the
+ * host path for one connection per call.
+ *
+ * l7g_mc_sessions_enable: max_pending > 0 turns them on (again: all sessions
+ * start empty), 0 turns them off and frees the memory.  Each connection's text
+ * queue is a ring of 16-byte intents (reply class, denied bit, the caller's
+ * tag) whose capacity C is the power of two that is at least max_pending (at
+ * most 65536: larger values return hipErrorInvalidValue), and each connection
+ * index has one 32-byte slot; both grow with the connection table.  Memory:
+ * (32 + 16 C) bytes per connection index, plus 64 bytes.  A host-only engine
+ * returns hipErrorNoDevice.  While sessions are off the other calls return
+ * hipErrorNotReady.
+ *
+ * l7g_mc_forward is the request direction (OnData(reply = false) of both
+ * parsers, from Matches on) for a batch: n requests on device memory as
+ * l7g_classify took them, with the verdicts it gave.  Request i takes part iff
+ * verdict[i] is L7G_ALLOW or L7G_DENY, conn[i] is a valid connection index
+ * whose protocol is memcached, its bytes lie inside the arena, and (text) its
+ * first line ends in "\r\n" inside the request and has a token -- which holds
+ * for every request l7g_classify answered ALLOW or DENY.  The requests of one
+ * connection are applied in batch order, by index, wherever they stand in the
+ * batch.  The parser (text or binary) is the one l7g_classify used: the
+ * connection's flag, else the request's first byte (>= 0x80: binary).  The
+ * first participating request -- or the first reply stream, below -- locks it
+ * in the slot; a later request of the other kind gets act 7, changes nothing
+ * and is counted.  A caller who wants the reference exactly sets the flag.
+ *   text: the command is the first token of bytes.Fields(first line); noreply
+ *   is decided by the token count for storage commands, delete, incr, decr and
+ *   touch, by the last token being "noreply" for flush_all and cache_memlimit,
+ *   and quit is always noreply; watch sets the connection's watching mode,
+ *   whatever the verdict.  An ALLOW that owes a reply is queued; a DENY that
+ *   owes one is answered at once iff the queue is empty, else queued as
+ *   denied; a noreply request changes nothing.
+ *   binary: requestCount advances; a DENY is answered at once iff requestCount
+ *   == replyCount + 1 (which advances replyCount), else it waits in the inject
+ *   queue as in the reference -- where, after the first DENY of a connection's
+ *   life has been injected, no later queued one is ever reached.
+ *   act[i]: 0 not handled; 1 pass, reply owed; 2 pass, noreply; 3 drop, send
+ *   the denied message now (binary: with byte 0 = request byte 0 | 0x81); 4
+ *   drop, the denied message is queued behind the replies still owed; 5 drop,
+ *   noreply; 6 the ring is full: nothing is queued and the caller must not
+ *   forward the request; 7 kind mismatch.  Within one call the pushes of a
+ *   connection succeed exactly while count < C, so every later pushing request
+ *   of that connection in the call is 6 as well; requests that push nothing go
+ *   on as usual.  Binary never answers 6.  The intent stores tag[i] (0 when
+ *   tag is NULL).  Scratch per stream, grow-only: 49 n bytes plus 16 bytes per
+ *   connection index plus the sort's and the scan's temporary storage; n is at
+ *   most 2^31 - 1.
+ *
+ * l7g_mc_replies is the reply direction: stream s is arena[s_off[s], +s_len[s])
+ * on connection s_conn[s], the reply bytes not yet passed, and the device runs
+ * the op loop of proxylib/proxylib/connection.go:118-174 over it with max_ops
+ * slots: until the ops are full; NOP ends it; an op of 0 bytes is
+ * PARSER_ERROR (ops already written stay); MORE ends it; PASS advances the
+ * input and the loop goes on, even over no input (so a queued inject follows
+ * the reply it waited for in the same call); ERROR 2 (a binary reply without
+ * bit 7 in its magic) neither advances nor ends the loop and fills the ops.
+ * The device has no inject buffer, so the reference's "inject buffer full"
+ * break never applies.  s_len 0 is legal: the "flush injects" call.  At most
+ * one stream per connection per call: with a second one that connection's
+ * results are unspecified (no memory outside its slot and ring is touched).
+ * Outputs, slots [s * max_ops, (s + 1) * max_ops):
+ *   op_kind  MORE 0, PASS 1, INJECT 3, ERROR 4 (FILTEROP_*)
+ *   op_n     the op's byte count (INJECT: 28 per denied text intent popped, 37
+ *            for the binary message; the bytes are l7g_mc_denied_message's)
+ *   op_aux   (may be NULL) a text PASS that popped an intent: that intent's
+ *            tag; a binary INJECT: the magic byte; else 0
+ *   nops[s]  ops written
+ *   result[s] 0 OK; 1 PARSER_ERROR; 2 not a memcached connection, an invalid
+ *            connection index or a stream outside the arena (no ops, no state
+ *            change); 3 no parser yet and no byte to make one from: no request
+ *            and no reply has locked a parser and s_len is 0 (the reference's
+ *            NOP; no ops, no state change).  With no parser yet and s_len > 0
+ *            the stream makes one as memcached/parser.go:186-202 does -- the
+ *            connection's flag, else the stream's first byte -- and runs.
+ *   taken[s] the sum of the PASS counts; a binary PASS may reach past the
+ *            bytes present, as in the reference.
+ * A stream whose ops fill max_ops ends there; a later call with the bytes from
+ * taken onward continues exactly where one call with more slots would have.
+ *
+ * The _host twins take host buffers on the calling thread's stream: inputs
+ * staged as for l7g_classify_host, the small outputs copied back (op slots
+ * past nops[s] come back 0); they synchronise.
+ *
+ * Resets: l7g_conn_update(index) is the new-connection event and empties that
+ * connection's session; l7g_conns_set empties all; l7g_mc_session_reset
+ * empties the named ones.  A policy update resets nothing.  Resets are applied
+ * before the next launch.
+ *
+ * The state is engine-wide, not per stream: calls that touch one connection
+ * (its requests, its replies, its resets) must be ordered by the caller, by
+ * issuing them on one stream; calls over disjoint connections may use
+ * different streams.
+ *
+ * l7g_mc_session_stats: [0] intents queued now, [1] connections with a
+ * session (a locked parser), [2] pushes refused (ring full), [3] kind
+ * mismatches, [4] denied messages due at once (act 3), [5] denied messages
+ * injected from the queue, [6] reply frames passed (text: PASS ops that popped
+ * an intent; binary: PASS ops), [7] parser errors; [2..7] since sessions were
+ * enabled.  Waits for the launched calls.  A host-only engine, or sessions
+ * off: zeros.
+ *
+ * l7g_mc_denied_message: the text parser's DeniedMsg (28 bytes) or, binary
+ * != 0, the binary parser's DeniedMsgBase (37 bytes; the sender sets byte 0). */
+int l7g_mc_sessions_enable(l7g_engine *e, uint32_t max_pending, char *err, size_t errlen);
+int l7g_mc_forward(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
+                   const uint32_t *conn, const uint8_t *verdict, const uint64_t *tag /* may be NULL */, uint32_t n,
+                   uint8_t *act, void *stream);
+int l7g_mc_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *s_off,
+                   const uint32_t *s_len, const uint32_t *s_conn, uint32_t n, uint32_t max_ops, uint8_t *op_kind,
+                   uint32_t *op_n, uint64_t *op_aux /* may be NULL */, uint32_t *nops, uint8_t *result, uint64_t *taken,
+                   void *stream);
+int l7g_mc_forward_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off,
+                        const uint32_t *len, const uint32_t *conn, const uint8_t *verdict, const uint64_t *tag,
+                        uint32_t n, uint8_t *act);
+int l7g_mc_replies_host(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *s_off,
+                        const uint32_t *s_len, const uint32_t *s_conn, uint32_t n, uint32_t max_ops, uint8_t *op_kind,
+                        uint32_t *op_n, uint64_t *op_aux, uint32_t *nops, uint8_t *result, uint64_t *taken);
+int l7g_mc_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n);
+void l7g_mc_session_stats(l7g_engine *e, uint64_t out[8]);
+const uint8_t *l7g_mc_denied_message(int binary, size_t *len);
 
 /* Resident services: the synchronous drop-in calls of l7g_classify_host (and
  * so the Envoy adapter's Allowed() and proxylib's OnData) whose requests are
