@@ -229,11 +229,13 @@ def _streams(w, rng, cut_every=5):
     return conns, streams, bounds
 
 
-def _run(engine, oracle, w, max_frames=64, extra=(), streams=None, align=1):
+def _run(engine, oracle, w, max_frames=64, extra=(), streams=None, align=1, gaps=None):
     """extra: (connection, stream) pairs appended to the generated streams;
     streams: (connections, streams, request boundaries) instead of the
     generated ones; align: each stream starts at an arena offset that is a
-    multiple of it (the device walk's windows then start at stream offset 0)."""
+    multiple of it (the device walk's windows then start at stream offset 0);
+    gaps: per stream, bytes left free before it (after the alignment: with
+    align=16, the stream's arena offset mod 16)."""
     rng = np.random.default_rng(7)
     engine.update_policy(w.policy)
     engine.set_connections(w.conns)
@@ -245,7 +247,7 @@ def _run(engine, oracle, w, max_frames=64, extra=(), streams=None, align=1):
     s_off = np.zeros(len(streams), np.uint64)
     parts, at = [], 0
     for k, st in enumerate(streams):
-        pad = (-at) % align
+        pad = (-at) % align + (gaps[k] if gaps is not None else 0)
         parts.append(b"\0" * pad)
         at += pad
         s_off[k] = at
