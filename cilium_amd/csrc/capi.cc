@@ -422,12 +422,9 @@ int l7g_conns_set(l7g_engine *e, const l7g_conn_t *conns, uint32_t n, char *err,
     e->attrs.assign(conns, conns + n);
     std::string m;
     if (!ResolveConns(e, &m)) { set_err(err, errlen, m); return -1; }
-    e->sess_reset_all = e->sess.by_id != nullptr;  // every connection is new
-    e->sess_reset.clear();
-    e->ksess_reset_all = e->ksess.tab != nullptr;
-    e->ksess_reset.clear();
-    e->mcsess_reset_all = e->mcsess.stats != nullptr;
-    e->mcsess_reset.clear();
+    e->sess_reset.All(e->sess.by_id != nullptr);  // every connection is new
+    e->ksess_reset.All(e->ksess.tab != nullptr);
+    e->mcsess_reset.All(e->mcsess.stats != nullptr);
     return 0;
 }
 
@@ -457,9 +454,9 @@ int l7g_conn_update(l7g_engine *e, uint32_t index, const l7g_conn_t *conn, char 
     }
     e->conns_dirty = true;
     // the new-connection event: proxylib makes a new parser there
-    if (e->sess.by_id && !e->sess_reset_all) e->sess_reset.push_back(index);
-    if (e->ksess.tab && !e->ksess_reset_all) e->ksess_reset.push_back(index);
-    if (e->mcsess.stats && !e->mcsess_reset_all) e->mcsess_reset.push_back(index);
+    e->sess_reset.Add(e->sess.by_id != nullptr, &index, 1);
+    e->ksess_reset.Add(e->ksess.tab != nullptr, &index, 1);
+    e->mcsess_reset.Add(e->mcsess.stats != nullptr, &index, 1);
     return 0;
 }
 

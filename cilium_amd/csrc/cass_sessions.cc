@@ -2,7 +2,8 @@
 // device tables (kernels/cassandra_session.hip) and l7g_cass_replies, the call
 // over device pointers that binds into them, on the caller's stream with that
 // stream's cassandra scratch.  l7g_classify reads and commits them in its own
-// plan (classify.cc).  The host-buffer twin is in host_call.cc.
+// plan (classify.cc).  The slot sync and the frame of the entries are
+// sessions.h's; the host-buffer twin is in host_call.cc.
 #include "sessions.h"
 
 static size_t TableBytes(const CassSessions &S) { return ((size_t)S.mask + 1) * sizeof(CassEntry); }
@@ -12,15 +13,14 @@ void SessionsFree(l7g_engine *e) {
     for (void *p : {(void *)e->sess.slots, (void *)e->sess.by_stream, (void *)e->sess.by_id, (void *)e->sess.stats})
         if (p) hipFree(p);
     e->sess = CassSessions{};
-    e->sess_reset.clear();
-    e->sess_reset_all = false;
+    e->sess_reset.Clear();
 }
 
 hipError_t SessionsSync(l7g_engine *e) {
     CassSessions &S = e->sess;
     if (!S.by_id) return hipSuccess;
     return SlotsSync(
-        e, S.slots, S.nslots, e->sess_reset, e->sess_reset_all,
+        e, S.slots, S.nslots, e->sess_reset,
         [&] {
             hipError_t r = hipMemsetAsync(S.by_stream, 0, TableBytes(S), nullptr);
             if (r == hipSuccess) r = hipMemsetAsync(S.by_id, 0, TableBytes(S), nullptr);
@@ -32,12 +32,11 @@ hipError_t SessionsSync(l7g_engine *e) {
 // l7g_cass_replies: the replies framed, the RESULT/prepared ones bound
 int CassReplies(l7g_engine *e, const DevIn &in, uint8_t *verdict, uint32_t *consumed, void *stream) {
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) return (int)hipErrorNoDevice;
-    if (!e->sess.by_id) return (int)hipErrorNotReady;  // sessions are off: nothing to bind into
+    hipError_t rc = Enter(e, e->sess.by_id != nullptr, kSyncCass);  // (sessions off: nothing to bind into)
+    if (rc != hipSuccess || in.n == 0) return (int)rc;
     hipStream_t s = (hipStream_t)stream;
     StreamScratch *S = nullptr;
-    hipError_t rc = CallBegin(e, kSyncCass, s, in.n ? &S : nullptr);
-    if (rc != hipSuccess || in.n == 0) return (int)rc;
+    if ((rc = GetScratch(e, s, &S)) != hipSuccess) return (int)rc;
     const size_t need = CassandraScratchBytes(in.n);
     if (need == 0) return (int)hipErrorInvalidValue;
     rc = S->Grow(&S->d_use, &S->use_cap, need, need);
@@ -51,10 +50,8 @@ extern "C" {
 
 int l7g_cass_sessions_enable(l7g_engine *e, uint32_t max_statements, char *err, size_t errlen) {
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) { set_err(err, errlen, "a host-only engine keeps no sessions"); return (int)hipErrorNoDevice; }
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = WaitLastClassify(e);
-    if (rc != hipSuccess) { set_err(err, errlen, hipGetErrorString(rc)); return (int)rc; }
+    hipError_t rc = EnableBegin(e, err, errlen);
+    if (rc != hipSuccess) return (int)rc;
     SessionsFree(e);
     if (max_statements == 0) return 0;
     // open addressing: twice the statements, so that probe chains stay short when all are held
@@ -70,13 +67,8 @@ int l7g_cass_sessions_enable(l7g_engine *e, uint32_t max_statements, char *err, 
     if (rc == hipSuccess) rc = hipMemsetAsync(S.by_stream, 0, tab, nullptr);
     if (rc == hipSuccess) rc = hipMemsetAsync(S.by_id, 0, tab, nullptr);
     if (rc == hipSuccess) rc = hipMemsetAsync(S.stats, 0, kStatBytes, nullptr);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(nullptr);
     e->sess = S;  // (the slots come with the first launch: SessionsSync)
-    if (rc != hipSuccess) {
-        SessionsFree(e);
-        set_err(err, errlen, hipGetErrorString(rc));
-    }
-    return (int)rc;
+    return EnableEnd(e, rc, SessionsFree, err, errlen);
 }
 
 int l7g_cass_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
@@ -86,30 +78,16 @@ int l7g_cass_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, co
 
 int l7g_cass_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n) {
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) return (int)hipErrorNoDevice;
-    if (!e->sess.by_id) return (int)hipErrorNotReady;
-    if (!e->sess_reset_all) e->sess_reset.insert(e->sess_reset.end(), conn, conn + n);
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = SessionsSync(e);
-    return (int)rc;
+    return SessionReset(e, e->sess.by_id != nullptr, e->sess_reset, conn, n, SessionsSync);
 }
 
 void l7g_cass_session_stats(l7g_engine *e, uint64_t out[6]) {
     std::lock_guard<std::mutex> g(e->mu);
     for (int k = 0; k < 6; k++) out[k] = 0;
-    if (e->device < 0 || !e->sess.by_id) return;
-    CassSessions &S = e->sess;
     unsigned long long h[CSS_WORDS + 2] = {};
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = SessionsSync(e);
-    if (rc == hipSuccess)
-        rc = Quiet(e, [&] {
-            hipError_t r = hipMemsetAsync(S.stats + CSS_WORDS, 0, 2 * sizeof(unsigned long long), nullptr);
-            if (r == hipSuccess) r = LaunchCassandraSessionLive(S, S.stats + CSS_WORDS, nullptr);
-            if (r == hipSuccess) r = hipMemcpyAsync(h, S.stats, sizeof h, hipMemcpyDeviceToHost, nullptr);
-            return r;
-        });
-    if (rc != hipSuccess) return;
+    if (!SessionStats(e, e->sess.by_id != nullptr, SessionsSync, e->sess.stats, CSS_WORDS, h,
+                      [&](unsigned long long *out2) { return LaunchCassandraSessionLive(e->sess, out2, nullptr); }))
+        return;
     out[0] = h[CSS_WORDS];
     out[1] = h[CSS_WORDS + 1];
     out[2] = h[CSS_DROPPED];

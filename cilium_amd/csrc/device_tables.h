@@ -539,10 +539,11 @@ struct KafkaSessions {
     KafkaSessEntry *spare;   // l7g_kafka_session_gc compacts into it, then the two swap
     unsigned long long *stats;  // KSS_*, then two words of the live count
 };
-// One l7g_kafka_forward / l7g_kafka_responses call as its kernels see it: frame
+// One call of the session kernels as they see it (kernels/sess_common.h): item
 // i is arena[offs[i] .. offs[i] + lens[i]) on connection conn_ids[i].
-struct KafkaSessBatch {
-    uint8_t *arena;  // (the correlation ids are rewritten in place)
+template <class Byte>
+struct SessBatchT {
+    Byte *arena;
     uint64_t arena_len;
     const uint64_t *offs;
     const uint32_t *lens;
@@ -550,6 +551,8 @@ struct KafkaSessBatch {
     const DevConn *conns;
     uint32_t n, nconns;
 };
+// l7g_kafka_forward / l7g_kafka_responses: frames (the correlation ids are rewritten in place)
+using KafkaSessBatch = SessBatchT<uint8_t>;
 
 // Memcached sessions (l7g_mc_sessions_enable; kernels/memcached_session.hip):
 // what proxylib's two memcached parsers keep per connection, resident in HBM.
@@ -594,17 +597,8 @@ struct McSessions {
     McSessIntent *ring;      // nslots * cap
     unsigned long long *stats;  // MSS_*, then two words of the live count
 };
-// One l7g_mc_forward / l7g_mc_replies call as its kernels see it: request (or
-// stream) i is arena[offs[i] .. offs[i] + lens[i]) on connection conn_ids[i].
-struct McSessBatch {
-    const uint8_t *arena;
-    uint64_t arena_len;
-    const uint64_t *offs;
-    const uint32_t *lens;
-    const uint32_t *conn_ids;
-    const DevConn *conns;
-    uint32_t n, nconns;
-};
+// l7g_mc_forward / l7g_mc_replies: requests (or reply streams), read only
+using McSessBatch = SessBatchT<const uint8_t>;
 // l7g_mc_replies' outputs (op_aux may be null)
 struct McReplyOut {
     uint8_t *op_kind;

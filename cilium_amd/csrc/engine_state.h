@@ -266,6 +266,15 @@ struct Service {
     }
 };
 
+// The new-connection events one protocol's device tables have not seen yet: connection indices, or every connection.
+struct SessionResets {
+    std::vector<uint32_t> pending;
+    bool all = false;
+    void Clear() { All(false); }
+    void All(bool on) { pending.clear(); all = on; }  // l7g_conns_set: every connection is new (on: sessions are)
+    void Add(bool on, const uint32_t *conn, size_t n) { if (on && !all) pending.insert(pending.end(), conn, conn + n); }
+};
+
 struct l7g_engine {
     int device = 0;
     // [0] HTTP, [1] memcached (l7g_service_enable; L7G_SERVICE=0 turns them off)
@@ -319,25 +328,22 @@ struct l7g_engine {
     bool flow_stats = false;
     uint64_t *d_flow = nullptr;
     size_t flow_cap = 0;  // keys the accumulator holds
-    // cassandra sessions (l7g_cass_sessions_enable; on while sess.by_id is set):
-    // the device tables (kernels/cassandra_session.hip), one slot per connection
-    // index grown with the connection table, and the new-connection events
-    // since the last launch (applied by SessionsSync before the next one)
+    // The sessions of three protocols, each kept the same way (sessions.h): the
+    // device tables, one slot per connection index grown with the connection
+    // table, and the new-connection events since the last launch (applied by
+    // the protocol's ...Sync before the next one).
+    // cassandra (l7g_cass_sessions_enable; on while sess.by_id is set; kernels/cassandra_session.hip)
     CassSessions sess{};
-    std::vector<uint32_t> sess_reset;
-    bool sess_reset_all = false;
-    // Kafka sessions (l7g_kafka_sessions_enable; on while ksess.tab is set), kept as the cassandra ones:
-    // the device tables (kernels/kafka_session.hip), one slot per connection index, the pending resets
+    SessionResets sess_reset;
+    // Kafka (l7g_kafka_sessions_enable; on while ksess.tab is set; kernels/kafka_session.hip)
     KafkaSessions ksess{};
-    std::vector<uint32_t> ksess_reset;
-    bool ksess_reset_all = false;
+    SessionResets ksess_reset;
     uint64_t ksess_expired = 0;  // entries l7g_kafka_session_gc dropped since enable
-    // memcached sessions (l7g_mc_sessions_enable; on while mcsess.stats is set), kept as the other two: one slot
-    // per connection index and its ring beside it (kernels/memcached_session.hip), the pending resets
+    // memcached (l7g_mc_sessions_enable; on while mcsess.stats is set; kernels/memcached_session.hip): a ring
+    // beside every slot
     McSessions mcsess{};
     uint32_t mcsess_ring_slots = 0;  // connections the ring has room for (follows mcsess.nslots)
-    std::vector<uint32_t> mcsess_reset;
-    bool mcsess_reset_all = false;
+    SessionResets mcsess_reset;
     // Every stream's last completion event (StreamScratch::done_ev) is waited
     // on -- never a caller's stream, which may be gone by then -- before the
     // engine rewrites or frees anything a launched kernel reads: the

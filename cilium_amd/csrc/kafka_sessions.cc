@@ -2,8 +2,8 @@
 // tables (kernels/kafka_session.hip) and the calls over device pointers,
 // l7g_kafka_forward and l7g_kafka_responses, each on the caller's stream with
 // that stream's scratch.  Nothing of l7g_classify's plan is involved.  The
-// slot sync is sessions.h's, shared with cass_sessions.cc; the host-buffer
-// twins are in host_call.cc.
+// slot sync and the frame of the entries are sessions.h's, as for every
+// protocol's sessions; the host-buffer twins are in host_call.cc.
 #include "sessions.h"
 
 namespace {
@@ -11,13 +11,7 @@ namespace {
 size_t TableBytes(const KafkaSessions &S) { return ((size_t)S.mask + 1) * sizeof(KafkaSessEntry); }
 constexpr size_t kStatBytes = (KSS_WORDS + 2) * sizeof(unsigned long long);
 
-// what every call here starts with (e->mu held): its checks, then CallBegin
-// with the Kafka sessions synced (the scratch follows the array checks)
-hipError_t Enter(l7g_engine *e) {
-    if (e->device < 0) return hipErrorNoDevice;
-    if (!e->ksess.tab) return hipErrorNotReady;
-    return CallBegin(e, kSyncKafka, nullptr, nullptr);
-}
+bool On(const l7g_engine *e) { return e->ksess.tab != nullptr; }
 
 }  // namespace
 
@@ -25,8 +19,7 @@ void KafkaSessionsFree(l7g_engine *e) {
     for (void *p : {(void *)e->ksess.slots, (void *)e->ksess.tab, (void *)e->ksess.spare, (void *)e->ksess.stats})
         if (p) hipFree(p);
     e->ksess = KafkaSessions{};
-    e->ksess_reset.clear();
-    e->ksess_reset_all = false;
+    e->ksess_reset.Clear();
     e->ksess_expired = 0;
 }
 
@@ -34,7 +27,7 @@ hipError_t KafkaSessionsSync(l7g_engine *e) {
     KafkaSessions &S = e->ksess;
     if (!S.tab) return hipSuccess;
     return SlotsSync(
-        e, S.slots, S.nslots, e->ksess_reset, e->ksess_reset_all,
+        e, S.slots, S.nslots, e->ksess_reset,
         [&] { return hipMemsetAsync(S.tab, 0, TableBytes(S), nullptr); },
         [&](const uint32_t *conn, uint32_t n) { return LaunchKafkaSessReset(S, conn, n, nullptr); });
 }
@@ -43,10 +36,8 @@ extern "C" {
 
 int l7g_kafka_sessions_enable(l7g_engine *e, uint32_t max_inflight, char *err, size_t errlen) {
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) { set_err(err, errlen, "a host-only engine keeps no sessions"); return (int)hipErrorNoDevice; }
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = WaitLastClassify(e);
-    if (rc != hipSuccess) { set_err(err, errlen, hipGetErrorString(rc)); return (int)rc; }
+    hipError_t rc = EnableBegin(e, err, errlen);
+    if (rc != hipSuccess) return (int)rc;
     KafkaSessionsFree(e);
     if (max_inflight == 0) return 0;
     if (max_inflight > (1u << 28)) { set_err(err, errlen, "max_inflight exceeds 2^28"); return (int)hipErrorInvalidValue; }
@@ -61,20 +52,15 @@ int l7g_kafka_sessions_enable(l7g_engine *e, uint32_t max_inflight, char *err, s
     if (rc == hipSuccess) rc = hipMalloc(&S.stats, kStatBytes);
     if (rc == hipSuccess) rc = hipMemsetAsync(S.tab, 0, tab, nullptr);
     if (rc == hipSuccess) rc = hipMemsetAsync(S.stats, 0, kStatBytes, nullptr);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(nullptr);
     e->ksess = S;  // (the slots come with the first call: KafkaSessionsSync)
-    if (rc != hipSuccess) {
-        KafkaSessionsFree(e);
-        set_err(err, errlen, hipGetErrorString(rc));
-    }
-    return (int)rc;
+    return EnableEnd(e, rc, KafkaSessionsFree, err, errlen);
 }
 
 int l7g_kafka_forward(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
                       const uint32_t *conn, const uint8_t *verdict, const uint64_t *tag, uint32_t n, uint64_t now_ms,
                       uint8_t *fwd, uint32_t *new_id, void *stream) {
     std::lock_guard<std::mutex> g(e->mu);
-    hipError_t rc = Enter(e);
+    hipError_t rc = Enter(e, On(e), kSyncKafka);
     if (rc != hipSuccess || n == 0) return (int)rc;
     if (!off || !len || !conn || !verdict || !fwd || !new_id) return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
@@ -93,7 +79,7 @@ int l7g_kafka_responses(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const
                         const uint32_t *conn, uint32_t n, uint8_t *found, uint32_t *orig_id, int16_t *api_key,
                         int16_t *api_version, uint64_t *tag, void *stream) {
     std::lock_guard<std::mutex> g(e->mu);
-    hipError_t rc = Enter(e);
+    hipError_t rc = Enter(e, On(e), kSyncKafka);
     if (rc != hipSuccess || n == 0) return (int)rc;
     if (!off || !len || !conn || !found || !orig_id || !api_key || !api_version || !tag) return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
@@ -109,7 +95,7 @@ int l7g_kafka_responses(l7g_engine *e, uint8_t *arena, uint64_t arena_len, const
 int l7g_kafka_session_gc(l7g_engine *e, uint64_t now_ms, uint64_t lifetime_ms, uint64_t *expired) {
     std::lock_guard<std::mutex> g(e->mu);
     if (expired) *expired = 0;
-    hipError_t rc = Enter(e);
+    hipError_t rc = Enter(e, On(e), kSyncKafka);
     if (rc != hipSuccess) return (int)rc;
     KafkaSessions &S = e->ksess;
     unsigned long long gone = 0;
@@ -129,30 +115,16 @@ int l7g_kafka_session_gc(l7g_engine *e, uint64_t now_ms, uint64_t lifetime_ms, u
 
 int l7g_kafka_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n) {
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) return (int)hipErrorNoDevice;
-    if (!e->ksess.tab) return (int)hipErrorNotReady;
-    if (!e->ksess_reset_all) e->ksess_reset.insert(e->ksess_reset.end(), conn, conn + n);
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = KafkaSessionsSync(e);
-    return (int)rc;
+    return SessionReset(e, On(e), e->ksess_reset, conn, n, KafkaSessionsSync);
 }
 
 void l7g_kafka_session_stats(l7g_engine *e, uint64_t out[7]) {
     std::lock_guard<std::mutex> g(e->mu);
     for (int k = 0; k < 7; k++) out[k] = 0;
-    if (e->device < 0 || !e->ksess.tab) return;
-    KafkaSessions &S = e->ksess;
     unsigned long long h[KSS_WORDS + 2] = {};
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = KafkaSessionsSync(e);
-    if (rc == hipSuccess)
-        rc = Quiet(e, [&] {
-            hipError_t r = hipMemsetAsync(S.stats + KSS_WORDS, 0, 2 * sizeof(unsigned long long), nullptr);
-            if (r == hipSuccess) r = LaunchKafkaSessLive(S, S.stats + KSS_WORDS, nullptr);
-            if (r == hipSuccess) r = hipMemcpyAsync(h, S.stats, sizeof h, hipMemcpyDeviceToHost, nullptr);
-            return r;
-        });
-    if (rc != hipSuccess) return;
+    if (!SessionStats(e, On(e), KafkaSessionsSync, e->ksess.stats, KSS_WORDS, h,
+                      [&](unsigned long long *out2) { return LaunchKafkaSessLive(e->ksess, out2, nullptr); }))
+        return;
     out[0] = h[KSS_WORDS];
     out[1] = h[KSS_WORDS + 1];
     out[2] = h[KSS_DROPPED];

@@ -8,9 +8,11 @@
 // its own connection's entries with plain loads, and of every other entry only
 // the claim word (an agent-scope atomic load).  Tables are never written while
 // a kernel looks statements up for verdicts: kernel boundaries on the caller's
-// stream are the only ordering between the two.
+// stream are the only ordering between the two.  The claim word itself is
+// sess_common.h's.
 #pragma once
 #include "cass_frame.h"
+#include "sess_common.h"
 
 namespace l7 {
 
@@ -22,14 +24,6 @@ __device__ __forceinline__ uint32_t cass_key_hash(uint32_t ci, const uint8_t *ke
     h *= 0x85EBCA6Bu;
     h ^= h >> 13;
     return h;
-}
-
-__device__ __forceinline__ unsigned long long cass_claim_of(uint32_t ci, uint32_t gen) {
-    return (unsigned long long)(ci + 1ull) << 32 | gen;
-}
-
-__device__ __forceinline__ unsigned long long cass_claim_load(const CassEntry *e) {
-    return __hip_atomic_load(&e->claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 __device__ __forceinline__ bool cass_key_eq(const CassEntry *e, const uint8_t *key, uint32_t n) {
@@ -44,7 +38,7 @@ __device__ inline CassEntry *cass_find(CassEntry *tab, uint32_t mask, unsigned l
                                        const uint8_t *key, uint32_t n) {
     uint32_t p = cass_key_hash(ci, key, n) & mask;
     for (uint32_t k = 0; k <= mask; k++, p = (p + 1) & mask) {
-        const unsigned long long c = cass_claim_load(&tab[p]);
+        const unsigned long long c = sess_claim_load(&tab[p]);
         if (c == 0) return nullptr;
         if (c == mine && cass_key_eq(&tab[p], key, n)) return &tab[p];
     }
@@ -64,7 +58,7 @@ __device__ inline CassEntry *cass_upsert(CassEntry *tab, uint32_t mask, const Ca
         uint32_t cand = 0;
         unsigned long long cand_claim = 0;
         for (uint32_t k = 0; k <= mask; k++, p = (p + 1) & mask) {
-            const unsigned long long c = cass_claim_load(&tab[p]);
+            const unsigned long long c = sess_claim_load(&tab[p]);
             if (c == mine) {
                 if (cass_key_eq(&tab[p], key, n)) return &tab[p];
                 continue;
@@ -74,8 +68,7 @@ __device__ inline CassEntry *cass_upsert(CassEntry *tab, uint32_t mask, const Ca
                 break;
             }
             if (!have) {
-                const uint32_t cj = (uint32_t)(c >> 32) - 1u;
-                if (cj >= nslots || slots[cj].gen != (uint32_t)c) { have = true; cand = p; cand_claim = c; }
+                if (!sess_claim_live(slots, nslots, c)) { have = true; cand = p; cand_claim = c; }
             }
         }
         if (!have) return nullptr;

@@ -278,7 +278,7 @@ __device__ __forceinline__ int cassandra_one(const Batch &B, const CassTables &T
                     const uint32_t il = cass_be16(b + 9);
                     const CassEntry *e = nullptr;
                     if (il <= kCassIdMax && ci < SS.nslots)  // (a longer id is never bound)
-                        e = cass_find(SS.by_id, SS.mask, cass_claim_of(ci, SS.slots[ci].gen), ci, b + 11, il);
+                        e = cass_find(SS.by_id, SS.mask, sess_claim_of(ci, SS.slots[ci].gen), ci, b + 11, il);
                     if (e && e->action != kCassTomb) {
                         stat = CSS_RESOLVED;
                         consumed = 0;
@@ -364,10 +364,6 @@ __global__ __launch_bounds__(kBlock) void cassandra_session_classify_kernel(Batc
     }
 }
 
-namespace {
-constexpr size_t KeyBytes(uint32_t n) { return ((size_t)n * sizeof(uint64_t) + 256 + 255) & ~(size_t)255; }
-}  // namespace
-
 // Scratch bytes LaunchCassandraClassify needs for a batch of n requests
 // (sessions: two more key arrays, the PREPARE marks and their sorted copy).
 size_t CassandraScratchBytes(uint32_t n, bool sessions) {
@@ -375,7 +371,7 @@ size_t CassandraScratchBytes(uint32_t n, bool sessions) {
     if (hipcub::DeviceRadixSort::SortKeys(nullptr, temp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)n, 0, 64) !=
         hipSuccess)
         return 0;
-    return (sessions ? 4 : 2) * KeyBytes(n) + ((temp + 255) & ~(size_t)255);  // as the launchers lay it out
+    return CassandraLayout(n, sessions, temp).total;
 }
 
 // scratch: CassandraScratchBytes(B.n) bytes (256-byte aligned)
@@ -383,12 +379,12 @@ size_t CassandraScratchBytes(uint32_t n, bool sessions) {
 hipError_t LaunchCassandraClassify(const Batch &B, const CassTables &T, void *scratch, size_t scratch_bytes,
                                    bool answer_other, uint32_t nfa_lanes, hipStream_t stream) {
     if (B.n == 0) return hipSuccess;
-    const size_t kb = KeyBytes(B.n);
-    uint64_t *keys = (uint64_t *)scratch;
-    uint64_t *sorted = (uint64_t *)((uint8_t *)scratch + kb);
-    void *temp = (uint8_t *)scratch + 2 * kb;
-    if (scratch_bytes < 2 * kb) return hipErrorInvalidValue;
-    size_t temp_bytes = scratch_bytes - 2 * kb;
+    const CassandraScratch L = CassandraLayout(B.n, false, 0);
+    if (scratch_bytes < L.temp) return hipErrorInvalidValue;
+    uint8_t *base = (uint8_t *)scratch;
+    uint64_t *keys = (uint64_t *)(base + L.keys), *sorted = (uint64_t *)(base + L.sorted);
+    void *temp = base + L.temp;
+    size_t temp_bytes = scratch_bytes - L.temp;
     const dim3 grid((B.n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(cassandra_use_kernel, grid, dim3(kBlock), 0, stream, B, T, keys);
     hipError_t rc = hipGetLastError();
@@ -411,13 +407,13 @@ static hipError_t SessionClassify(const Batch &B, const CassTables &T, const Cas
                                   size_t scratch_bytes, bool answer_other, uint32_t nfa_lanes, hipStream_t stream,
                                   bool commit) {
     if (B.n == 0) return hipSuccess;
-    const size_t kb = KeyBytes(B.n);
+    const CassandraScratch L = CassandraLayout(B.n, true, 0);
+    if (scratch_bytes < L.temp) return hipErrorInvalidValue;
     uint8_t *base = (uint8_t *)scratch;
-    uint64_t *keys = (uint64_t *)base, *sorted = (uint64_t *)(base + kb);
-    uint64_t *pkeys = (uint64_t *)(base + 2 * kb), *psorted = (uint64_t *)(base + 3 * kb);
-    void *temp = base + 4 * kb;
-    if (scratch_bytes < 4 * kb) return hipErrorInvalidValue;
-    size_t temp_bytes = scratch_bytes - 4 * kb;
+    uint64_t *keys = (uint64_t *)(base + L.keys), *sorted = (uint64_t *)(base + L.sorted);
+    uint64_t *pkeys = (uint64_t *)(base + L.pkeys), *psorted = (uint64_t *)(base + L.psorted);
+    void *temp = base + L.temp;
+    size_t temp_bytes = scratch_bytes - L.temp;
     const dim3 grid((B.n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(cassandra_marks_kernel, grid, dim3(kBlock), 0, stream, B, T, keys, pkeys);
     hipError_t rc = hipGetLastError();
@@ -451,9 +447,9 @@ hipError_t LaunchCassandraSessionClassifyLogged(const Batch &B, const CassTables
     if (B.n == 0) return hipSuccess;
     hipError_t rc = SessionClassify(B, T, SS, scratch, scratch_bytes, answer_other, nfa_lanes, stream, false);
     if (rc != hipSuccess) return rc;
-    const size_t kb = KeyBytes(B.n);
-    const uint64_t *sorted = (const uint64_t *)((uint8_t *)scratch + kb);
-    const uint64_t *psorted = (const uint64_t *)((uint8_t *)scratch + 3 * kb);
+    const CassandraScratch at = CassandraLayout(B.n, true, 0);
+    const uint64_t *sorted = (const uint64_t *)((uint8_t *)scratch + at.sorted);
+    const uint64_t *psorted = (const uint64_t *)((uint8_t *)scratch + at.psorted);
     rc = LaunchGenericLog(B, L, X, T, sorted, SS, stream);
     if (rc != hipSuccess) return rc;
     return LaunchCassandraCommit(B, T, SS, sorted, psorted, stream);
@@ -461,7 +457,8 @@ hipError_t LaunchCassandraSessionClassifyLogged(const Batch &B, const CassTables
 
 // The sorted USE keys the launchers above left in `scratch` for a batch of n requests.
 const uint64_t *CassandraSortedUseKeys(const void *scratch, uint32_t n) {
-    return (const uint64_t *)((const uint8_t *)scratch + KeyBytes(n));
+    // (the sorted USE keys lie at one offset with sessions and without)
+    return (const uint64_t *)((const uint8_t *)scratch + CassandraLayout(n, false, 0).sorted);
 }
 
 }  // namespace l7

@@ -54,11 +54,6 @@ struct PathSink {
     }
 };
 
-// Is sorted[j] the first key of its connection?
-__device__ __forceinline__ bool segment_head(const uint64_t *__restrict__ sorted, uint32_t j) {
-    return j == 0 || (sorted[j - 1] >> 32) != (sorted[j] >> 32);
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kBlock) void cass_commit_prepares_kernel(Batch B, CassTables T, CassSessions S,
@@ -66,12 +61,12 @@ __global__ __launch_bounds__(kBlock) void cass_commit_prepares_kernel(Batch B, C
                                                                       const uint64_t *__restrict__ prep_sorted) {
     uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= B.n || prep_sorted[j] == ~0ull || !segment_head(prep_sorted, j)) return;
-    const uint32_t ci = (uint32_t)(prep_sorted[j] >> 32);
+    const uint32_t ci = key_conn(prep_sorted[j]);
     if (ci >= S.nslots) return;
     CassSlot *slot = &S.slots[ci];
-    const unsigned long long mine = cass_claim_of(ci, slot->gen);
-    for (; j < B.n && prep_sorted[j] != ~0ull && (uint32_t)(prep_sorted[j] >> 32) == ci; j++) {
-        const uint32_t i = (uint32_t)prep_sorted[j];
+    const unsigned long long mine = sess_claim_of(ci, slot->gen);
+    for (; j < B.n && prep_sorted[j] != ~0ull && key_conn(prep_sorted[j]) == ci; j++) {
+        const uint32_t i = key_index(prep_sorted[j]);
         // (a complete PREPARE frame whose query parses: cassandra_marks_kernel)
         const uint8_t *b = B.arena + B.offs[i];
         const CassQuery Q = cass_parse_query(b + 13, cass_be32(b + 9), T.lower, T.nlower);
@@ -111,11 +106,11 @@ __global__ __launch_bounds__(kBlock) void cass_commit_keyspace_kernel(Batch B, C
                                                                       const uint64_t *__restrict__ use_sorted) {
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= B.n || use_sorted[j] == ~0ull) return;
-    const uint32_t ci = (uint32_t)(use_sorted[j] >> 32);
+    const uint32_t ci = key_conn(use_sorted[j]);
     // the connection's last USE of the batch only
-    if (j + 1 < B.n && use_sorted[j + 1] != ~0ull && (uint32_t)(use_sorted[j + 1] >> 32) == ci) return;
+    if (j + 1 < B.n && use_sorted[j + 1] != ~0ull && key_conn(use_sorted[j + 1]) == ci) return;
     if (ci >= S.nslots) return;
-    const uint32_t i = (uint32_t)use_sorted[j];
+    const uint32_t i = key_index(use_sorted[j]);
     const uint8_t *q = B.arena + B.offs[i] + 13;
     const CassQuery Q = cass_parse_query(q, cass_be32(q - 4), T.lower, T.nlower);
     CassSlot *slot = &S.slots[ci];
@@ -162,7 +157,7 @@ __global__ __launch_bounds__(kBlock) void cass_replies_kernel(Batch B, uint64_t 
                     verdict = V_PARSE_ERROR;  // data[9:13] panics
                 } else if (cass_be32(d + 9) == 4) {
                     if (len < 15 || 15u + cass_be16(d + 13) > len) verdict = V_PARSE_ERROR;  // the id's slices panic
-                    else keys[i] = (uint64_t)ci << 32 | i;
+                    else keys[i] = sess_key(ci, i);
                 }
                 if (verdict == V_PARSE_ERROR) consumed = 0;
             }
@@ -176,12 +171,12 @@ __global__ __launch_bounds__(kBlock) void cass_commit_binds_kernel(Batch B, Cass
                                                                    const uint64_t *__restrict__ sorted) {
     uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= B.n || sorted[j] == ~0ull || !segment_head(sorted, j)) return;
-    const uint32_t ci = (uint32_t)(sorted[j] >> 32);
+    const uint32_t ci = key_conn(sorted[j]);
     if (ci >= S.nslots) return;
     const CassSlot *slot = &S.slots[ci];
-    const unsigned long long mine = cass_claim_of(ci, slot->gen);
-    for (; j < B.n && sorted[j] != ~0ull && (uint32_t)(sorted[j] >> 32) == ci; j++) {
-        const uint8_t *d = B.arena + B.offs[(uint32_t)sorted[j]];
+    const unsigned long long mine = sess_claim_of(ci, slot->gen);
+    for (; j < B.n && sorted[j] != ~0ull && key_conn(sorted[j]) == ci; j++) {
+        const uint8_t *d = B.arena + B.offs[key_index(sorted[j])];
         const uint32_t il = cass_be16(d + 13);
         const uint8_t *id = d + 15;
         const CassEntry *st = cass_find(S.by_stream, S.mask, mine, ci, d + 2, 2);
@@ -234,8 +229,7 @@ __global__ __launch_bounds__(kBlock) void cass_live_kernel(CassSessions S, unsig
         const CassEntry *e = &tabs[t][p];
         const unsigned long long c = e->claim;
         if (c == 0 || e->action == kCassTomb) continue;
-        const uint32_t cj = (uint32_t)(c >> 32) - 1u;
-        if (cj < S.nslots && S.slots[cj].gen == (uint32_t)c) atomicAdd(&out[t], 1ull);
+        if (sess_claim_live(S.slots, S.nslots, c)) atomicAdd(&out[t], 1ull);
     }
 }
 
@@ -253,11 +247,12 @@ hipError_t LaunchCassandraCommit(const Batch &B, const CassTables &T, const Cass
 hipError_t LaunchCassandraReplies(const Batch &B, const CassSessions &S, void *scratch, size_t scratch_bytes,
                                   hipStream_t stream) {
     if (B.n == 0) return hipSuccess;
-    const size_t kb = ((size_t)B.n * sizeof(uint64_t) + 256 + 255) & ~(size_t)255;
-    if (scratch_bytes < 2 * kb) return hipErrorInvalidValue;
-    uint64_t *keys = (uint64_t *)scratch, *sorted = (uint64_t *)((uint8_t *)scratch + kb);
-    void *temp = (uint8_t *)scratch + 2 * kb;
-    size_t temp_bytes = scratch_bytes - 2 * kb;
+    const CassandraScratch L = CassandraLayout(B.n, false, 0);
+    if (scratch_bytes < L.temp) return hipErrorInvalidValue;
+    uint8_t *base = (uint8_t *)scratch;
+    uint64_t *keys = (uint64_t *)(base + L.keys), *sorted = (uint64_t *)(base + L.sorted);
+    void *temp = base + L.temp;
+    size_t temp_bytes = scratch_bytes - L.temp;
     const dim3 grid((B.n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(cass_replies_kernel, grid, dim3(kBlock), 0, stream, B, keys);
     hipError_t rc = hipGetLastError();

@@ -249,7 +249,7 @@ __device__ __forceinline__ void cass_log(const Batch &B, const uint8_t *b, uint3
         if (len < 11) return;
         const uint32_t il = cass_be16(b + 9);
         if (il > kCassIdMax || 11u + il > len || ci >= SS.nslots) return;
-        const CassEntry *e = cass_find(SS.by_id, SS.mask, cass_claim_of(ci, SS.slots[ci].gen), ci, b + 11, il);
+        const CassEntry *e = cass_find(SS.by_id, SS.mask, sess_claim_of(ci, SS.slots[ci].gen), ci, b + 11, il);
         if (!e || e->action == kCassTomb || e->path_len == kCassOver) return;
         action = e->action;
         if (action < 0) flags |= 4;  // a statement keeps no action word

@@ -7,9 +7,10 @@
 // no other.  A lane that probes past an entry it did not claim reads of it
 // only the claim word (an agent-scope atomic load); payloads are read by
 // later kernels alone.  Kernel boundaries on the caller's stream are the only
-// ordering between the two.
+// ordering between the two.  The claim word itself is sess_common.h's; the
+// deleted value (kKafkaSessDeleted) names no connection, so it reads as stale.
 #pragma once
-#include "../device_tables.h"
+#include "sess_common.h"
 
 namespace l7 {
 
@@ -23,27 +24,12 @@ __device__ __forceinline__ uint32_t ksess_hash(uint32_t ci, uint32_t id) {
     return h;
 }
 
-__device__ __forceinline__ unsigned long long ksess_claim_of(uint32_t ci, uint32_t gen) {
-    return (unsigned long long)(ci + 1ull) << 32 | gen;
-}
-
-__device__ __forceinline__ unsigned long long ksess_claim_load(const KafkaSessEntry *e) {
-    return __hip_atomic_load(&e->claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Does claim word c (not 0) still resolve?  The deleted value names no
-// connection, so it reads as stale like a claim of a connection that moved on.
-__device__ __forceinline__ bool ksess_live(const KafkaSessions &S, unsigned long long c) {
-    const uint32_t cj = (uint32_t)(c >> 32) - 1u;
-    return cj < S.nslots && S.slots[cj].gen == (uint32_t)c;
-}
-
 // The entry of (mine, id) in tab, or null.  Only a never-used slot ends the chain.
 __device__ inline KafkaSessEntry *ksess_find(KafkaSessEntry *tab, uint32_t mask, unsigned long long mine, uint32_t ci,
                                              uint32_t id) {
     uint32_t p = ksess_hash(ci, id) & mask;
     for (uint32_t k = 0; k <= mask; k++, p = (p + 1) & mask) {
-        const unsigned long long c = ksess_claim_load(&tab[p]);
+        const unsigned long long c = sess_claim_load(&tab[p]);
         if (c == 0) return nullptr;
         if (c == mine && tab[p].id == id) return &tab[p];
     }
@@ -58,8 +44,8 @@ __device__ inline KafkaSessEntry *ksess_claim(const KafkaSessions &S, KafkaSessE
                                               uint32_t ci, uint32_t id) {
     uint32_t p = ksess_hash(ci, id) & S.mask;
     for (uint32_t k = 0; k <= S.mask; k++, p = (p + 1) & S.mask) {
-        const unsigned long long c = ksess_claim_load(&tab[p]);
-        if (c != 0 && ksess_live(S, c)) continue;
+        const unsigned long long c = sess_claim_load(&tab[p]);
+        if (c != 0 && sess_claim_live(S.slots, S.nslots, c)) continue;
         if (atomicCAS(&tab[p].claim, c, mine) == c) return &tab[p];
     }
     return nullptr;

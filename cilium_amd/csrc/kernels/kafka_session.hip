@@ -23,14 +23,11 @@
 // l7g_kafka_session_gc: ksess_gc_kernel re-inserts every live, unexpired entry
 // of the table into the spare one (zeroed first); the host swaps the two.
 //
-// Every grid is capped at kMaxBlocks workgroups and strides above that; loops
+// Every grid is capped at kSessMaxBlocks workgroups and strides above that; loops
 // are uniform per wave so that the statistics take one atomic per wave.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <algorithm>
-
-#include "../device_tables.h"
 #include "kafka_session.h"
 #include "launch.h"
 
@@ -38,18 +35,8 @@ namespace l7 {
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr uint32_t kMaxBlocks = 4096;  // every grid's ceiling; grid-stride above it
-
-inline dim3 GridFor(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, kMaxBlocks)); }
-inline size_t Align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// bits of a connection index, the value nconns (the keys of requests not forwarded) included
-inline int ConnBits(uint32_t nconns) {
-    int b = 1;
-    while (b < 32 && (nconns >> b)) b++;
-    return b;
-}
+constexpr int kBlock = kSessBlock;
+static_assert(sizeof(uint2) == kKafkaSegBytes, "seg[] as sess_scratch.h lays it out");
 
 __device__ __forceinline__ uint32_t be_bytes(const uint8_t *p, int k) {
     uint32_t v = 0;
@@ -69,19 +56,6 @@ __device__ __forceinline__ void put_be32(uint8_t *p, uint32_t v) {
     }
 }
 
-// *w += the lanes of the wave with pred set (every lane of the wave calls it)
-__device__ __forceinline__ void wave_count(unsigned long long *w, bool pred) {
-    const unsigned long long m = __ballot(pred);
-    if (m && __lane_id() == (unsigned)__ffsll((long long)m) - 1u) atomicAdd(w, (unsigned long long)__popcll(m));
-}
-
-// a frame of a Kafka connection that lies inside the arena
-__device__ __forceinline__ bool kafka_frame(const KafkaSessBatch &B, const KafkaSessions &S, uint32_t i) {
-    const uint32_t ci = B.conn_ids[i];
-    return ci < B.nconns && ci < S.nslots && B.conns[ci].proto == PROTO_KAFKA &&
-           l7_in_arena(B.offs[i], B.lens[i], B.arena_len);
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kBlock) void ksess_keys_kernel(KafkaSessBatch B, KafkaSessions S,
@@ -89,8 +63,8 @@ __global__ __launch_bounds__(kBlock) void ksess_keys_kernel(KafkaSessBatch B, Ka
                                                             uint64_t *__restrict__ keys, uint8_t *__restrict__ fwd,
                                                             uint32_t *__restrict__ new_id) {
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < B.n; i += (uint64_t)gridDim.x * kBlock) {
-        const bool go = verdict[i] == V_ALLOW && kafka_frame(B, S, (uint32_t)i);
-        keys[i] = (uint64_t)(go ? B.conn_ids[i] : B.nconns) << 32 | i;
+        const bool go = verdict[i] == V_ALLOW && sess_item(B, S.nslots, PROTO_KAFKA, (uint32_t)i);
+        keys[i] = sess_key(go ? B.conn_ids[i] : B.nconns, (uint32_t)i);
         if (!go) {
             fwd[i] = 0;
             new_id[i] = 0;
@@ -103,17 +77,12 @@ __global__ __launch_bounds__(kBlock) void ksess_heads_kernel(KafkaSessBatch B, K
                                                              const uint64_t *__restrict__ sorted,
                                                              uint2 *__restrict__ seg) {
     for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < B.n; j += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t ci = (uint32_t)(sorted[j] >> 32);
-        if (ci >= B.nconns || (j && (uint32_t)(sorted[j - 1] >> 32) == ci)) continue;
-        // the first position past this connection's keys
-        uint64_t lo = j + 1, hi = B.n;
-        while (lo < hi) {
-            const uint64_t m = lo + (hi - lo) / 2;
-            if ((uint32_t)(sorted[m] >> 32) == ci) lo = m + 1; else hi = m;
-        }
+        const uint32_t ci = key_conn(sorted[j]);
+        if (ci >= B.nconns || !segment_head(sorted, j)) continue;
+        const uint64_t end = segment_end(sorted, j, B.n, ci);
         KafkaSessSlot *slot = &S.slots[ci];
         seg[ci] = make_uint2((uint32_t)j, slot->seq);
-        slot->seq += (uint32_t)(lo - j);
+        slot->seq += (uint32_t)(end - j);
     }
 }
 
@@ -124,15 +93,15 @@ __global__ __launch_bounds__(kBlock) void ksess_insert_kernel(KafkaSessBatch B, 
                                                               uint8_t *__restrict__ fwd, uint32_t *__restrict__ new_id) {
     for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < B.n; base += (uint64_t)gridDim.x * kBlock) {
         const uint64_t j = base + threadIdx.x;
-        const uint32_t ci = j < B.n ? (uint32_t)(sorted[j] >> 32) : B.nconns;
+        const uint32_t ci = j < B.n ? key_conn(sorted[j]) : B.nconns;
         bool kept = false, dropped = false;
         if (ci < B.nconns) {
-            const uint32_t i = (uint32_t)sorted[j];
+            const uint32_t i = key_index(sorted[j]);
             const uint2 sg = seg[ci];
             const uint32_t id = sg.y + 1u + ((uint32_t)j - sg.x);
             uint8_t *r = B.arena + B.offs[i];
             const uint32_t len = B.lens[i];
-            KafkaSessEntry *e = ksess_claim(S, S.tab, ksess_claim_of(ci, S.slots[ci].gen), ci, id);
+            KafkaSessEntry *e = ksess_claim(S, S.tab, sess_claim_of(ci, S.slots[ci].gen), ci, id);
             if (e) {
                 e->id = id;
                 e->orig = len >= 12 ? be_bytes(r + 8, 4) : 0;
@@ -158,10 +127,10 @@ __global__ __launch_bounds__(kBlock) void ksess_probe_kernel(KafkaSessBatch B, K
                                                              uint32_t *__restrict__ where) {
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < B.n; i += (uint64_t)gridDim.x * kBlock) {
         uint32_t at = ~0u;
-        if (kafka_frame(B, S, (uint32_t)i)) {
+        if (sess_item(B, S.nslots, PROTO_KAFKA, (uint32_t)i)) {
             const uint32_t ci = B.conn_ids[i];
             const uint32_t id = B.lens[i] >= 8 ? be_bytes(B.arena + B.offs[i] + 4, 4) : 0;
-            KafkaSessEntry *e = ksess_find(S.tab, S.mask, ksess_claim_of(ci, S.slots[ci].gen), ci, id);
+            KafkaSessEntry *e = ksess_find(S.tab, S.mask, sess_claim_of(ci, S.slots[ci].gen), ci, id);
             if (e) {
                 at = (uint32_t)(e - S.tab);
                 atomicMin(&e->taker, (uint32_t)i);
@@ -207,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void ksess_gc_kernel(KafkaSessions S, uint6
         if (p <= S.mask) {
             const KafkaSessEntry *e = &S.tab[p];
             const unsigned long long c = e->claim;
-            if (c != 0 && ksess_live(S, c)) {
+            if (c != 0 && sess_claim_live(S.slots, S.nslots, c)) {
                 const uint64_t age = now_ms > e->created_ms ? now_ms - e->created_ms : 0;
                 old = age >= lifetime_ms;
                 if (!old) {
@@ -245,7 +214,7 @@ __global__ __launch_bounds__(kBlock) void ksess_live_kernel(KafkaSessions S, uns
     for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base <= S.mask; base += (uint64_t)gridDim.x * kBlock) {
         const uint64_t p = base + threadIdx.x;
         const unsigned long long c = p <= S.mask ? S.tab[p].claim : 0;
-        wave_count(&out[0], c != 0 && ksess_live(S, c));
+        wave_count(&out[0], c != 0 && sess_claim_live(S.slots, S.nslots, c));
         wave_count(&out[1], c != 0);
     }
 }
@@ -256,21 +225,20 @@ size_t KafkaSessForwardScratchBytes(uint32_t n, uint32_t nconns) {
         hipcub::DeviceRadixSort::SortKeys(nullptr, temp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)n, 0,
                                           32 + ConnBits(nconns)) != hipSuccess)
         return 0;
-    // as LaunchKafkaSessForward lays it out
-    return 2 * Align256((size_t)n * 8 + 256) + Align256(((size_t)nconns + 1) * sizeof(uint2)) + Align256(temp);
+    return KafkaForwardLayout(n, nconns, temp).total;
 }
 
 hipError_t LaunchKafkaSessForward(const KafkaSessBatch &B, const KafkaSessions &S, const uint8_t *verdict,
                                   const uint64_t *tag, uint64_t now_ms, uint8_t *fwd, uint32_t *new_id, void *scratch,
                                   size_t scratch_bytes, hipStream_t stream) {
     if (B.n == 0) return hipSuccess;
-    const size_t kb = Align256((size_t)B.n * 8 + 256), sb = Align256(((size_t)B.nconns + 1) * sizeof(uint2));
-    if (scratch_bytes < 2 * kb + sb) return hipErrorInvalidValue;
+    const KafkaForwardScratch L = KafkaForwardLayout(B.n, B.nconns, 0);
+    if (scratch_bytes < L.temp) return hipErrorInvalidValue;
     uint8_t *base = (uint8_t *)scratch;
-    uint64_t *keys = (uint64_t *)base, *sorted = (uint64_t *)(base + kb);
-    uint2 *seg = (uint2 *)(base + 2 * kb);
-    void *temp = base + 2 * kb + sb;
-    size_t temp_bytes = scratch_bytes - 2 * kb - sb;
+    uint64_t *keys = (uint64_t *)(base + L.keys), *sorted = (uint64_t *)(base + L.sorted);
+    uint2 *seg = (uint2 *)(base + L.seg);
+    void *temp = base + L.temp;
+    size_t temp_bytes = scratch_bytes - L.temp;
     const dim3 grid = GridFor(B.n), block(kBlock);
     hipLaunchKernelGGL(ksess_keys_kernel, grid, block, 0, stream, B, S, verdict, keys, fwd, new_id);
     hipError_t rc = hipGetLastError();
@@ -285,14 +253,15 @@ hipError_t LaunchKafkaSessForward(const KafkaSessBatch &B, const KafkaSessions &
     return hipGetLastError();
 }
 
-size_t KafkaSessResponsesScratchBytes(uint32_t n) { return Align256((size_t)n * 4 + 256); }
+size_t KafkaSessResponsesScratchBytes(uint32_t n) { return KafkaResponsesLayout(n).total; }
 
 hipError_t LaunchKafkaSessResponses(const KafkaSessBatch &B, const KafkaSessions &S, uint8_t *found, uint32_t *orig_id,
                                     int16_t *api_key, int16_t *api_version, uint64_t *tag, void *scratch,
                                     size_t scratch_bytes, hipStream_t stream) {
     if (B.n == 0) return hipSuccess;
-    if (scratch_bytes < KafkaSessResponsesScratchBytes(B.n)) return hipErrorInvalidValue;
-    uint32_t *where = (uint32_t *)scratch;
+    const KafkaResponsesScratch L = KafkaResponsesLayout(B.n);
+    if (scratch_bytes < L.total) return hipErrorInvalidValue;
+    uint32_t *where = (uint32_t *)((uint8_t *)scratch + L.where);
     const dim3 grid = GridFor(B.n), block(kBlock);
     hipLaunchKernelGGL(ksess_probe_kernel, grid, block, 0, stream, B, S, where);
     hipError_t rc = hipGetLastError();

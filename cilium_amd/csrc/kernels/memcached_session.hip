@@ -29,50 +29,28 @@
 // The slot and the ring are read by resolve and written by advance (the slot)
 // and resolve (ring entries past the queued ones): kernel boundaries on the
 // caller's stream are the only ordering, there is no flag between workgroups.
-// Every grid is capped at kMaxBlocks workgroups and strides above that; loops
+// Every grid is capped at kSessMaxBlocks workgroups and strides above that; loops
 // are uniform per wave so that the statistics take one atomic per wave.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 
-#include "../device_tables.h"
 #include "launch.h"
 #include "mc_session.h"
+#include "sess_common.h"
 
 namespace l7 {
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr uint32_t kMaxBlocks = 4096;  // every grid's ceiling; grid-stride above it
-
-inline dim3 GridFor(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, kMaxBlocks)); }
-inline size_t Align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// bits of a connection index, the value nconns (the keys of requests that take no part) included
-inline int ConnBits(uint32_t nconns) {
-    int b = 1;
-    while (b < 32 && (nconns >> b)) b++;
-    return b;
-}
-
-// *w += the lanes of the wave with pred set (every lane of the wave calls it)
-__device__ __forceinline__ void wave_count(unsigned long long *w, bool pred) {
-    const unsigned long long m = __ballot(pred);
-    if (m && __lane_id() == (unsigned)__ffsll((long long)m) - 1u) atomicAdd(w, (unsigned long long)__popcll(m));
-}
-
-// (connection, bytes) of a memcached connection with a slot, inside the arena
-__device__ __forceinline__ bool mc_item(const McSessBatch &B, const McSessions &S, uint32_t i) {
-    const uint32_t ci = B.conn_ids[i];
-    return ci < B.nconns && ci < S.nslots && B.conns[ci].proto == PROTO_MEMCACHE &&
-           l7_in_arena(B.offs[i], B.lens[i], B.arena_len);
-}
+constexpr int kBlock = kSessBlock;
 
 struct McSeg {
     uint32_t start, end, kind, pad;
 };
+static_assert(sizeof(McSeg) == kMcSegBytes && sizeof(McScan) == kMcScanBytes,
+              "seg[], el[] and sc[] as sess_scratch.h lays them out");
 
 // replies - requests of a binary slot; the immediate injects of a segment are
 // the DENYs from position g + 1 (1-based) up to the next ALLOW, none for g < 0
@@ -87,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void mcsess_keys_kernel(McSessBatch B, McSe
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < B.n; i += (uint64_t)gridDim.x * kBlock) {
         const uint8_t v = verdict[i];
         uint32_t bits = 0;
-        if ((v == V_ALLOW || v == V_DENY) && B.lens[i] != 0 && mc_item(B, S, (uint32_t)i)) {
+        if ((v == V_ALLOW || v == V_DENY) && B.lens[i] != 0 && sess_item(B, S.nslots, PROTO_MEMCACHE, (uint32_t)i)) {
             const uint8_t *b = B.arena + B.offs[i];
             McReader W{b, ~0ull, 0, 0};
             // the parser, as the classifier picks it: the connection's flags, else the first byte
@@ -97,7 +75,7 @@ __global__ __launch_bounds__(kBlock) void mcsess_keys_kernel(McSessBatch B, McSe
             else bits = mcs_text_request(mcs_line(W, 0, B.lens[i]));
             if (bits && v == V_DENY) bits |= MCI_DENY;
         }
-        keys[i] = (uint64_t)(bits ? B.conn_ids[i] : B.nconns) << 32 | i;
+        keys[i] = sess_key(bits ? B.conn_ids[i] : B.nconns, (uint32_t)i);
         info[i] = (uint8_t)bits;
         if (!bits) act[i] = 0;
     }
@@ -109,17 +87,12 @@ __global__ __launch_bounds__(kBlock) void mcsess_heads_kernel(McSessBatch B, McS
                                                               const uint8_t *__restrict__ info,
                                                               McSeg *__restrict__ seg) {
     for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < B.n; j += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t ci = (uint32_t)(sorted[j] >> 32);
-        if (ci >= B.nconns || (j && (uint32_t)(sorted[j - 1] >> 32) == ci)) continue;
-        // the first position past this connection's keys
-        uint64_t lo = j + 1, hi = B.n;
-        while (lo < hi) {
-            const uint64_t m = lo + (hi - lo) / 2;
-            if ((uint32_t)(sorted[m] >> 32) == ci) lo = m + 1; else hi = m;
-        }
+        const uint32_t ci = key_conn(sorted[j]);
+        if (ci >= B.nconns || !segment_head(sorted, j)) continue;
+        const uint64_t end = segment_end(sorted, j, B.n, ci);
         uint32_t kind = S.slots[ci].kind;
-        if (kind == MCK_NONE) kind = (info[(uint32_t)sorted[j]] & MCI_BINARY) ? MCK_BINARY : MCK_TEXT;
-        seg[ci] = McSeg{(uint32_t)j, (uint32_t)lo, kind, 0};
+        if (kind == MCK_NONE) kind = (info[key_index(sorted[j])] & MCI_BINARY) ? MCK_BINARY : MCK_TEXT;
+        seg[ci] = McSeg{(uint32_t)j, (uint32_t)end, kind, 0};
     }
 }
 
@@ -127,11 +100,11 @@ __global__ __launch_bounds__(kBlock) void mcsess_elems_kernel(McSessBatch B, con
                                                               const uint8_t *__restrict__ info,
                                                               const McSeg *__restrict__ seg, McScan *__restrict__ el) {
     for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < B.n; j += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t ci = (uint32_t)(sorted[j] >> 32);
+        const uint32_t ci = key_conn(sorted[j]);
         McScan x{MCS_HEAD, 0, 0, 0};
         if (ci < B.nconns) {
             const McSeg sg = seg[ci];
-            const uint32_t in = info[(uint32_t)sorted[j]];
+            const uint32_t in = info[key_index(sorted[j])];
             const bool bin = sg.kind == MCK_BINARY, deny = (in & MCI_DENY) != 0;
             x.f = ((uint32_t)j == sg.start ? MCS_HEAD : 0u) | (bin ? MCS_BIN : 0u);
             if (bin == ((in & MCI_BINARY) != 0)) {  // (a request of the other parser changes nothing)
@@ -161,10 +134,10 @@ __global__ __launch_bounds__(kBlock) void mcsess_resolve_kernel(McSessBatch B, M
                                                                 uint8_t *__restrict__ act) {
     for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < B.n; base += (uint64_t)gridDim.x * kBlock) {
         const uint64_t j = base + threadIdx.x;
-        const uint32_t ci = j < B.n ? (uint32_t)(sorted[j] >> 32) : B.nconns;
+        const uint32_t ci = j < B.n ? key_conn(sorted[j]) : B.nconns;
         bool full = false, mismatch = false, now = false;
         if (ci < B.nconns) {
-            const uint32_t i = (uint32_t)sorted[j];
+            const uint32_t i = key_index(sorted[j]);
             const uint32_t in = info[i];
             const McSeg sg = seg[ci];
             const McSessSlot sl = S.slots[ci];
@@ -217,8 +190,8 @@ __global__ __launch_bounds__(kBlock) void mcsess_advance_kernel(McSessBatch B, M
                                                                 const McSeg *__restrict__ seg,
                                                                 const McScan *__restrict__ sc) {
     for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < B.n; j += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t ci = (uint32_t)(sorted[j] >> 32);
-        if (ci >= B.nconns || (j && (uint32_t)(sorted[j - 1] >> 32) == ci)) continue;
+        const uint32_t ci = key_conn(sorted[j]);
+        if (ci >= B.nconns || !segment_head(sorted, j, ci)) continue;
         const McSeg sg = seg[ci];
         const McScan tot = sc[sg.end - 1];
         McSessSlot sl = S.slots[ci];
@@ -245,7 +218,7 @@ __global__ __launch_bounds__(kBlock) void mcsess_advance_kernel(McSessBatch B, M
                     const uint32_t m = lo + (hi - lo) / 2;
                     if (sc[m].d) hi = m; else lo = m + 1;
                 }
-                const uint32_t i = (uint32_t)sorted[lo];
+                const uint32_t i = key_index(sorted[lo]);
                 const bool now = g >= 0 && (int64_t)tot.d > g && (int64_t)sc[lo].a <= g;
                 sl.bstate = now ? MCB_BLOCKED : MCB_ARMED;
                 sl.armed_id = sl.requests + tot.d;
@@ -386,7 +359,7 @@ __global__ __launch_bounds__(kBlock) void mcsess_replies_kernel(McSessBatch B, M
         ReplyRun R{0, 0, 0, 0, 0};
         McSessSlot sl{};
         uint32_t ci = 0;
-        if (!mc_item(B, S, (uint32_t)s)) {
+        if (!sess_item(B, S.nslots, PROTO_MEMCACHE, (uint32_t)s)) {
             R.result = 2;
         } else {
             ci = B.conn_ids[s];
@@ -442,25 +415,21 @@ size_t McSessForwardScratchBytes(uint32_t n, uint32_t nconns) {
         hipcub::DeviceScan::InclusiveScan(nullptr, scan_temp, (const McScan *)nullptr, (McScan *)nullptr, McScanOp{},
                                           (int)n) != hipSuccess)
         return 0;
-    // as LaunchMcSessForward lays it out
-    return 2 * Align256((size_t)n * 8 + 256) + Align256((size_t)n + 256) + 2 * Align256((size_t)n * sizeof(McScan) + 256) +
-           Align256(((size_t)nconns + 1) * sizeof(McSeg)) + Align256(std::max(sort_temp, scan_temp));
+    return McForwardLayout(n, nconns, std::max(sort_temp, scan_temp)).total;
 }
 
 hipError_t LaunchMcSessForward(const McSessBatch &B, const McSessions &S, const uint8_t *verdict, const uint64_t *tag,
                                uint8_t *act, void *scratch, size_t scratch_bytes, hipStream_t stream) {
     if (B.n == 0) return hipSuccess;
-    const size_t kb = Align256((size_t)B.n * 8 + 256), ib = Align256((size_t)B.n + 256);
-    const size_t eb = Align256((size_t)B.n * sizeof(McScan) + 256), sb = Align256(((size_t)B.nconns + 1) * sizeof(McSeg));
-    const size_t fixed = 2 * kb + ib + 2 * eb + sb;
-    if (scratch_bytes < fixed) return hipErrorInvalidValue;
+    const McForwardScratch L = McForwardLayout(B.n, B.nconns, 0);
+    if (scratch_bytes < L.temp) return hipErrorInvalidValue;
     uint8_t *base = (uint8_t *)scratch;
-    uint64_t *keys = (uint64_t *)base, *sorted = (uint64_t *)(base + kb);
-    uint8_t *info = base + 2 * kb;
-    McScan *el = (McScan *)(base + 2 * kb + ib), *sc = (McScan *)(base + 2 * kb + ib + eb);
-    McSeg *seg = (McSeg *)(base + 2 * kb + ib + 2 * eb);
-    void *temp = base + fixed;
-    size_t temp_bytes = scratch_bytes - fixed;
+    uint64_t *keys = (uint64_t *)(base + L.keys), *sorted = (uint64_t *)(base + L.sorted);
+    uint8_t *info = base + L.info;
+    McScan *el = (McScan *)(base + L.el), *sc = (McScan *)(base + L.sc);
+    McSeg *seg = (McSeg *)(base + L.seg);
+    void *temp = base + L.temp;
+    size_t temp_bytes = scratch_bytes - L.temp;
     const dim3 grid = GridFor(B.n), block(kBlock);
     hipLaunchKernelGGL(mcsess_keys_kernel, grid, block, 0, stream, B, S, verdict, keys, info, act);
     hipError_t rc = hipGetLastError();

@@ -2,8 +2,8 @@
 // device state (kernels/memcached_session.hip) and the calls over device
 // pointers, l7g_mc_forward and l7g_mc_replies, each on the caller's stream
 // with that stream's scratch.  Nothing of l7g_classify's plan is involved.
-// The slot sync is sessions.h's, shared with cass_sessions.cc and
-// kafka_sessions.cc; the ring grows beside the slots here.  The host-buffer
+// The slot sync and the frame of the entries are sessions.h's, as for every
+// protocol's sessions; the ring grows beside the slots here.  The host-buffer
 // twins are in host_call.cc.
 #include "deny_templates.h"
 #include "sessions.h"
@@ -18,13 +18,7 @@ static_assert(sizeof(l7::kMcDeniedText) - 1 == kMcDeniedTextLen && sizeof(l7::kM
 
 size_t RingBytes(const McSessions &S, uint32_t slots) { return (size_t)slots * S.cap * sizeof(McSessIntent); }
 
-// what every call here starts with (e->mu held): its checks, then CallBegin
-// with the memcached sessions synced (the scratch follows the array checks)
-hipError_t Enter(l7g_engine *e) {
-    if (e->device < 0) return hipErrorNoDevice;
-    if (!e->mcsess.stats) return hipErrorNotReady;
-    return CallBegin(e, kSyncMc, nullptr, nullptr);
-}
+bool On(const l7g_engine *e) { return e->mcsess.stats != nullptr; }
 
 }  // namespace
 
@@ -33,8 +27,7 @@ void McSessionsFree(l7g_engine *e) {
         if (p) hipFree(p);
     e->mcsess = McSessions{};
     e->mcsess_ring_slots = 0;
-    e->mcsess_reset.clear();
-    e->mcsess_reset_all = false;
+    e->mcsess_reset.Clear();
 }
 
 hipError_t McSessionsSync(l7g_engine *e) {
@@ -42,7 +35,7 @@ hipError_t McSessionsSync(l7g_engine *e) {
     if (!S.stats) return hipSuccess;
     // (a zeroed slot queues nothing: the ring's bytes need no reset)
     hipError_t rc = SlotsSync(
-        e, S.slots, S.nslots, e->mcsess_reset, e->mcsess_reset_all, [] { return hipSuccess; },
+        e, S.slots, S.nslots, e->mcsess_reset, [] { return hipSuccess; },
         [&](const uint32_t *conn, uint32_t n) { return LaunchMcSessReset(S, conn, n, nullptr); });
     if (rc != hipSuccess || S.nslots <= e->mcsess_ring_slots) return rc;
     // the ring beside the slots: connection c's entries stay at c * cap
@@ -65,10 +58,8 @@ extern "C" {
 
 int l7g_mc_sessions_enable(l7g_engine *e, uint32_t max_pending, char *err, size_t errlen) {
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) { set_err(err, errlen, "a host-only engine keeps no sessions"); return (int)hipErrorNoDevice; }
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = WaitLastClassify(e);
-    if (rc != hipSuccess) { set_err(err, errlen, hipGetErrorString(rc)); return (int)rc; }
+    hipError_t rc = EnableBegin(e, err, errlen);
+    if (rc != hipSuccess) return (int)rc;
     McSessionsFree(e);
     if (max_pending == 0) return 0;
     if (max_pending > kMaxRing) { set_err(err, errlen, "max_pending exceeds 65536"); return (int)hipErrorInvalidValue; }
@@ -77,20 +68,15 @@ int l7g_mc_sessions_enable(l7g_engine *e, uint32_t max_pending, char *err, size_
     while (S.cap < max_pending) S.cap <<= 1;
     rc = hipMalloc(&S.stats, kStatBytes);
     if (rc == hipSuccess) rc = hipMemsetAsync(S.stats, 0, kStatBytes, nullptr);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(nullptr);
     e->mcsess = S;  // (the slots and the ring come with the first call: McSessionsSync)
-    if (rc != hipSuccess) {
-        McSessionsFree(e);
-        set_err(err, errlen, hipGetErrorString(rc));
-    }
-    return (int)rc;
+    return EnableEnd(e, rc, McSessionsFree, err, errlen);
 }
 
 int l7g_mc_forward(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, const uint64_t *off, const uint32_t *len,
                    const uint32_t *conn, const uint8_t *verdict, const uint64_t *tag, uint32_t n, uint8_t *act,
                    void *stream) {
     std::lock_guard<std::mutex> g(e->mu);
-    hipError_t rc = Enter(e);
+    hipError_t rc = Enter(e, On(e), kSyncMc);
     if (rc != hipSuccess || n == 0) return (int)rc;
     if (!off || !len || !conn || !verdict || !act) return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
@@ -109,7 +95,7 @@ int l7g_mc_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, cons
                    const uint32_t *s_len, const uint32_t *s_conn, uint32_t n, uint32_t max_ops, uint8_t *op_kind,
                    uint32_t *op_n, uint64_t *op_aux, uint32_t *nops, uint8_t *result, uint64_t *taken, void *stream) {
     std::lock_guard<std::mutex> g(e->mu);
-    hipError_t rc = Enter(e);
+    hipError_t rc = Enter(e, On(e), kSyncMc);
     if (rc != hipSuccess || n == 0) return (int)rc;
     if (!s_off || !s_len || !s_conn || !nops || !result || !taken || (max_ops && (!op_kind || !op_n)))
         return (int)hipErrorInvalidValue;
@@ -123,30 +109,16 @@ int l7g_mc_replies(l7g_engine *e, const uint8_t *arena, uint64_t arena_len, cons
 
 int l7g_mc_session_reset(l7g_engine *e, const uint32_t *conn, uint32_t n) {
     std::lock_guard<std::mutex> g(e->mu);
-    if (e->device < 0) return (int)hipErrorNoDevice;
-    if (!e->mcsess.stats) return (int)hipErrorNotReady;
-    if (!e->mcsess_reset_all) e->mcsess_reset.insert(e->mcsess_reset.end(), conn, conn + n);
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = McSessionsSync(e);
-    return (int)rc;
+    return SessionReset(e, On(e), e->mcsess_reset, conn, n, McSessionsSync);
 }
 
 void l7g_mc_session_stats(l7g_engine *e, uint64_t out[8]) {
     std::lock_guard<std::mutex> g(e->mu);
     for (int k = 0; k < 8; k++) out[k] = 0;
-    if (e->device < 0 || !e->mcsess.stats) return;
-    McSessions &S = e->mcsess;
     unsigned long long h[MSS_WORDS + 2] = {};
-    hipError_t rc = hipSetDevice(e->device);
-    if (rc == hipSuccess) rc = McSessionsSync(e);
-    if (rc == hipSuccess)
-        rc = Quiet(e, [&] {
-            hipError_t r = hipMemsetAsync(S.stats + MSS_WORDS, 0, 2 * sizeof(unsigned long long), nullptr);
-            if (r == hipSuccess) r = LaunchMcSessLive(S, S.stats + MSS_WORDS, nullptr);
-            if (r == hipSuccess) r = hipMemcpyAsync(h, S.stats, sizeof h, hipMemcpyDeviceToHost, nullptr);
-            return r;
-        });
-    if (rc != hipSuccess) return;
+    if (!SessionStats(e, On(e), McSessionsSync, e->mcsess.stats, MSS_WORDS, h,
+                      [&](unsigned long long *out2) { return LaunchMcSessLive(e->mcsess, out2, nullptr); }))
+        return;
     out[0] = h[MSS_WORDS];
     out[1] = h[MSS_WORDS + 1];
     for (int k = 0; k < MSS_WORDS; k++) out[2 + k] = h[k];

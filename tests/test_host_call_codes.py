@@ -3,7 +3,8 @@ behind them, on a host-only engine.  Each entry checks its arguments and the
 device in an order of its own (l7g_classify_logged_host rejects a null log
 before it looks at the device; l7g_deny_replies_host reports no-device first),
 and callers see that order in the code they get.  The table below was recorded
-from the library before its entries came to share their prologue; run this
+from the library before its entries came to share their prologue (the memcached
+rows before the three protocols' session entries came to share theirs); run this
 file as a script to print the table of the library as built.  Nothing here
 reaches a GPU call."""
 import ctypes as C
@@ -41,6 +42,12 @@ EXPECTED = {
     "l7g_cass_session_reset": {"sessions_off": 100},
     "l7g_kafka_session_reset": {"sessions_off": 100},
     "l7g_kafka_session_gc": {"sessions_off": 100},
+    "l7g_mc_forward": {"ok": 100, "n0": 100, "null_arrays": 100, "null_outputs": 100},
+    "l7g_mc_forward_host": {"ok": 100, "n0": 100, "null_arrays": 100, "null_outputs": 100},
+    "l7g_mc_replies": {"ok": 100, "n0": 100, "null_arrays": 100, "null_outputs": 100},
+    "l7g_mc_replies_host": {"ok": 100, "n0": 100, "null_arrays": 100, "null_outputs": 100},
+    "l7g_mc_sessions_enable": {"on": 100, "off": 100},
+    "l7g_mc_session_reset": {"sessions_off": 100},
 }
 
 
@@ -160,11 +167,28 @@ def table():
         got["l7g_kafka_responses"] = {c: L.l7g_kafka_responses(h, *resp_args(c), None) for c in common}
         got["l7g_kafka_responses_host"] = {c: L.l7g_kafka_responses_host(h, *resp_args(c)) for c in common}
 
+        def mc_fwd_args(c):
+            out = (None,) if c == "null_outputs" else (_p(b.fwd),)
+            return (*inputs(c)[:5], v_in(c), None, inputs(c)[5], *out)
+
+        def mc_rep_args(c):
+            out = (None,) * 6 if c == "null_outputs" else (_p(b.fwd), _p(b.ids), _p(b.tag), _p(b.r_len), _p(b.verdict),
+                                                           _p(b.total))
+            return (*inputs(c), 1, *out)
+
+        got["l7g_mc_forward"] = {c: L.l7g_mc_forward(h, *mc_fwd_args(c), None) for c in common}
+        got["l7g_mc_forward_host"] = {c: L.l7g_mc_forward_host(h, *mc_fwd_args(c)) for c in common}
+        got["l7g_mc_replies"] = {c: L.l7g_mc_replies(h, *mc_rep_args(c), None) for c in common}
+        got["l7g_mc_replies_host"] = {c: L.l7g_mc_replies_host(h, *mc_rep_args(c)) for c in common}
+
         err = C.create_string_buffer(256)
         got["l7g_cass_sessions_enable"] = {"on": L.l7g_cass_sessions_enable(h, 64, err, 256),
                                            "off": L.l7g_cass_sessions_enable(h, 0, err, 256)}
         got["l7g_kafka_sessions_enable"] = {"on": L.l7g_kafka_sessions_enable(h, 64, err, 256),
                                             "off": L.l7g_kafka_sessions_enable(h, 0, err, 256)}
+        got["l7g_mc_sessions_enable"] = {"on": L.l7g_mc_sessions_enable(h, 64, err, 256),
+                                         "off": L.l7g_mc_sessions_enable(h, 0, err, 256)}
+        got["l7g_mc_session_reset"] = {"sessions_off": L.l7g_mc_session_reset(h, _p(b.conn), 1)}
         got["l7g_cass_session_reset"] = {"sessions_off": L.l7g_cass_session_reset(h, _p(b.conn), 1)}
         got["l7g_kafka_session_reset"] = {"sessions_off": L.l7g_kafka_session_reset(h, _p(b.conn), 1)}
         gone = C.c_uint64(7)

@@ -57,7 +57,7 @@ def from_code_object(path, pat):
         if pat in name or pat.replace("::", "") in f["name"]:
             rows.append((name, f))
     print(f"{'kernel':70s} {'lds_B':>7s} {'scratch_B':>9s} {'vgprs':>5s} {'sgprs':>5s} {'wg':>5s} {'vspill':>6s} {'sspill':>6s}")
-    for name, f in sorted(rows):
+    for name, f in sorted(rows, key=lambda r: (r[0], r[1]["name"])):  # (two kernels may print one name)
         print(f"{name[:70]:70s} {int(f['group_segment_fixed_size']):7d} {int(f['private_segment_fixed_size']):9d} "
               f"{int(f['vgpr_count']):5d} {int(f['sgpr_count']):5d} {int(f['max_flat_workgroup_size']):5d} "
               f"{int(f.get('vgpr_spill_count', 0)):6d} {int(f.get('sgpr_spill_count', 0)):6d}")
