@@ -10,6 +10,17 @@
 #define L7G_KAFKA_HELPER 1
 #endif
 
+int l7::DeviceCuCount() {
+    static const int cus = [] {
+        int dev = 0, c = 0;
+        return hipGetDevice(&dev) == hipSuccess &&
+                       hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && c > 0
+                   ? c
+                   : 256;
+    }();
+    return cus;
+}
+
 // Waits for the kernels of every stream's last call, and stops the services
 // (their launch arguments are what the caller is about to rewrite).  Caller
 // holds e->mu.

@@ -84,6 +84,14 @@ struct Batch {
     uint32_t *consumed;
     uint32_t n, nconns;
 };
+// The connection a request names (ci: its id, read twice); an id past the table
+// reads as no connection: no parser, no rule set.  A macro, since through a
+// function, in any form, the 8 bytes are loaded differently and every reader's
+// registers move.  (An own-protocol connection without a rule set is answered
+// UNSUPPORTED by HTTP, Kafka and memcached and left alone by cassandra and
+// r2d2; set_connections refuses such connections.)
+#define L7_CONN(conns, nconns, ci) ((ci) < (nconns) ? (conns)[ci] : DevConn{-1, PROTO_NONE, 0, 0xFFFF})
+#define L7_BATCH_CONN(B, ci) L7_CONN((B).conns, (B).nconns, ci)
 
 // The access-log outputs of a logged call (l7g_log_out_t, include/l7gpu.h):
 // one 32-byte record per request, written as two 16-byte stores, and a row of
@@ -288,6 +296,20 @@ struct HttpTables {
     uint64_t *nfa_scratch;     // large NFAs: nfa_lane_words per lane of the launch (null: none in the pool)
     uint32_t nfa_lane_words;
 };
+// Who answers an entry on a connection (its DevConn::ruleset and ::proto: the
+// two fields, not the struct, which as an argument is loaded as one word and
+// moves the callers' registers).  Entries of the other owned protocols belong
+// to their own kernels; the HTTP kernels answer HTTP's and those whose
+// connection is unknown or has no parser.
+struct HttpConnClass {
+    bool mine;        // HTTP's to answer
+    int32_t ruleset;  // the HTTP rule set to classify it on; -1: none (mine: answered UNSUPPORTED)
+};
+L7_HD inline HttpConnClass l7_http_conn_class(int32_t ruleset, uint32_t proto, const HttpTables &T) {
+    const bool mine = !L7_PROTO_OWNED(proto) || proto == PROTO_HTTP;
+    const bool http = mine && proto == PROTO_HTTP && ruleset >= 0 && (uint32_t)ruleset < T.nrulesets;
+    return HttpConnClass{mine, http ? ruleset : -1};
+}
 
 // ---------------- Kafka ----------------
 // Rule semantics: pkg/kafka/policy.go ruleMatches :144-195 / MatchesRule :200-225.

@@ -229,7 +229,7 @@ __device__ __forceinline__ int cassandra_one(const Batch &B, const CassTables &T
                                              uint32_t answer_other, uint32_t i, uint64_t *scratch,
                                              const CassSessions &SS) {
     const uint32_t ci = B.conn_ids[i];
-    const DevConn conn = ci < B.nconns ? B.conns[ci] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
+    const DevConn conn = L7_BATCH_CONN(B, ci);
     if (conn.proto != PROTO_CASSANDRA || conn.ruleset < 0 || (uint32_t)conn.ruleset >= T.nrulesets) {
         if (answer_other && !L7_PROTO_OWNED(conn.proto)) {  // no parser: UNSUPPORTED
             B.verdict[i] = V_UNSUPPORTED;

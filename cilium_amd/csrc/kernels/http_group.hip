@@ -31,11 +31,10 @@ constexpr int kPer = 8;  // entries per thread
 // entry i of `sel` (the partition's HTTP list, ListEnt: its index) or request i.
 __device__ __forceinline__ int32_t group_rs(const Batch &B, const HttpTables &T, uint32_t idx, bool &other) {
     const uint32_t ci = B.conn_ids[idx];
-    const DevConn c = ci < B.nconns ? B.conns[ci] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
-    const bool mine = !L7_PROTO_OWNED(c.proto) || c.proto == PROTO_HTTP;
-    const bool http = mine && c.proto == PROTO_HTTP && c.ruleset >= 0 && (uint32_t)c.ruleset < T.nrulesets;
-    other = mine && !http;
-    return http ? c.ruleset : -1;
+    const DevConn conn = L7_BATCH_CONN(B, ci);
+    const HttpConnClass c = l7_http_conn_class(conn.ruleset, conn.proto, T);
+    other = c.mine && c.ruleset < 0;
+    return c.ruleset;
 }
 
 // hist[r] += the entries on rule set r

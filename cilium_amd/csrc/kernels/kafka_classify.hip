@@ -725,7 +725,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
             idx = sel[(size_t)c * n + j];
         }
         const uint32_t ci = B.conn_ids[idx];
-        const DevConn conn = ci < nconns ? B.conns[ci] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
+        const DevConn conn = L7_CONN(B.conns, nconns, ci);
         const uint64_t off = B.offs[idx];
         const uint32_t len = B.lens[idx];
         uint8_t verdict = V_PARSE_ERROR;
@@ -803,20 +803,13 @@ hipError_t LaunchKafkaClassify(const Batch &B, const KafkaTables &T, const uint3
     const auto kernel = lg ? kafka_classify_kernel<4, true>
                            : (beside ? kafka_classify_kernel<6, false> : kafka_classify_kernel<5, false>);
     // persistent grid: as many workgroups as the CUs hold at once (per build)
-    static int cus[2][2] = {}, per_cu[2][2] = {};
-    if (cus[lg][beside] == 0) {
-        int dev = 0, c = 0, p = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, kernel, kBlock, 0) == hipSuccess && c > 0 && p > 0) {
-            per_cu[lg][beside] = p;
-            cus[lg][beside] = c;
-        } else {
-            per_cu[lg][beside] = 32;
-            cus[lg][beside] = 256;
-        }
+    static int per_cu[2][2] = {};
+    if (per_cu[lg][beside] == 0) {
+        int p = 0;
+        per_cu[lg][beside] =
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, kernel, kBlock, 0) == hipSuccess && p > 0 ? p : 32;
     }
-    const int pc = per_cu[lg][beside], ncu = cus[lg][beside];
+    const int pc = per_cu[lg][beside], ncu = DeviceCuCount();
     const int slots = beside && pc > leave_per_cu ? pc - leave_per_cu : pc;
     if (!work) blocks = blocks > 8192 ? 8192 : blocks;  // grid-stride beyond this
     else if (blocks > (uint32_t)(ncu * slots)) blocks = (uint32_t)(ncu * slots);

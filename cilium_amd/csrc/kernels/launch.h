@@ -10,6 +10,9 @@
 
 namespace l7 {
 
+// The current device's CU count (classify.cc), for the persistent grids: asked once per process, 256
+// when the runtime does not say.
+int DeviceCuCount();
 // sel (here, LaunchHttpGroup, LaunchMemcacheClassify): entry lists (ListEnt, device_tables.h)
 hipError_t LaunchHttpClassify(const Batch &B, const HttpTables &T, const ListEnt *sel, const uint32_t *sel_count,
                               bool any_cold, bool answer_other, uint32_t *tile_ctr, bool latency, const CopyIn *ci,

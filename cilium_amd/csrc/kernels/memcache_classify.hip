@@ -506,7 +506,7 @@ __device__ __forceinline__ void mc_one(const Batch &B, const McTables &T, const 
     const uint32_t ci = B.conn_ids[idx];
     const uint64_t off = B.offs[idx];
     const uint32_t len = B.lens[idx];
-    const DevConn conn = ci < B.nconns ? B.conns[ci] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
+    const DevConn conn = L7_BATCH_CONN(B, ci);
     mc_body<kNfa, kLds, kCh>(B, T, images, idx, off, len, conn, answer_other);
 }
 
@@ -520,7 +520,7 @@ __device__ __forceinline__ void mc_entries(const Batch &B, const uint32_t (&ix)[
 #pragma unroll
     for (int r = 0; r < kMcSortPer; r++) ci[r] = ix[r] != ~0u ? B.conn_ids[ix[r]] : ~0u;
 #pragma unroll
-    for (int r = 0; r < kMcSortPer; r++) c[r] = ci[r] < B.nconns ? B.conns[ci[r]] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
+    for (int r = 0; r < kMcSortPer; r++) c[r] = L7_BATCH_CONN(B, ci[r]);
 #pragma unroll
     for (int r = 0; r < kMcSortPer; r++) {
         e[r] = make_uint4(ix[r], 0, 0, kEntByIndex);
@@ -768,17 +768,7 @@ __global__ __launch_bounds__(kBlock) void memcache_classify_sync_kernel(Batch B,
 }
 
 // workgroups the device holds at once in `per_cu` slots per CU
-static uint32_t BesideBlocks(int per_cu) {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, c = 0;
-        cus = hipGetDevice(&dev) == hipSuccess &&
-                      hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && c > 0
-                  ? c
-                  : 256;
-    }
-    return (uint32_t)(cus * per_cu);
-}
+static uint32_t BesideBlocks(int per_cu) { return (uint32_t)(DeviceCuCount() * per_cu); }
 
 // Beside Kafka the kernel runs at wave priority 3, as a persistent grid (other
 // values in variant builds, for A/B; profiles/beside_leg/ab_variants_visit*.txt)

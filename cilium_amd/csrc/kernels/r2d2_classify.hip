@@ -45,7 +45,7 @@ __device__ __forceinline__ uint32_t rd(Win &r, const uint8_t *p) {
 __device__ __forceinline__ void r2d2_one(const Batch &B, const R2Tables &T, uint32_t answer_other, uint32_t i,
                                          uint64_t *scratch) {
     const uint32_t ci = B.conn_ids[i];
-    const DevConn conn = ci < B.nconns ? B.conns[ci] : DevConn{-1, PROTO_NONE, 0, 0xFFFF};
+    const DevConn conn = L7_BATCH_CONN(B, ci);
     if (conn.proto != PROTO_R2D2 || conn.ruleset < 0 || (uint32_t)conn.ruleset >= T.nrulesets) {
         if (answer_other && !L7_PROTO_OWNED(conn.proto)) {
             B.verdict[i] = V_UNSUPPORTED;

@@ -207,3 +207,28 @@ def test_grouped_path(ctx):
     got = _run(ctx, ctx.d_arena, w.offsets[idx], w.lengths[idx], w.conn_ids[idx])
     assert_same(got, tuple(r[idx] for r in ctx.ref), gen.Workload("t", w.arena, w.offsets[idx], w.lengths[idx],
                                                                   w.conn_ids[idx], w.conns, w.policy))
+
+
+def test_grouped_path_outside_the_arena(ctx):
+    """The grouped kernel's own out-of-arena branch: test_grouped_path's tiling
+    with every 13th request of an owned protocol moved out of the arena, the
+    four ways of test_requests_outside_the_arena; HTTP requests of the hot and
+    of the cold rule set are among them."""
+    w = ctx.w
+    n = 65536 + 17
+    idx = np.arange(n) % N
+    offs, lens, cids = w.offsets[idx].copy(), w.lengths[idx].copy(), w.conn_ids[idx]
+    ref = [r[idx].copy() for r in ctx.ref]
+    proto = ctx.proto[idx]
+    bad = np.nonzero(proto != 0)[0][::13]
+    A = len(w.arena)
+    kind = np.arange(len(bad)) % 4
+    offs[bad[kind == 0]] = A + 4096
+    offs[bad[kind == 1]], lens[bad[kind == 1]] = A - 1, 2
+    offs[bad[kind == 2]] += np.uint64(1 << 42)
+    offs[bad[kind == 3]] = 1 << 62
+    ref[0][bad], ref[1][bad], ref[2][bad] = UNSUPPORTED, -1, 0
+    moved_http = bad[proto[bad] == PROTO_HTTP]
+    assert (cids[moved_http] < 4).any() and ((cids[moved_http] >= 4) & (cids[moved_http] < 6)).any()
+    got = _run(ctx, ctx.d_arena, offs, lens, cids)
+    assert_same(got, tuple(ref), gen.Workload("t", w.arena, offs, lens, cids, w.conns, w.policy))

@@ -1,4 +1,4 @@
-"""The latency path's well-formed-head shortcut (http_classify.hip:lat_fast)
+"""The latency path's well-formed-head shortcut (http_lat.h:lat_fast)
 against the oracle, bit-exact.
 
 Calls of at most 64 requests run one request per wave; a head that meets

@@ -1,5 +1,5 @@
 """The HTTP latency kernel (one request per wave, its header lines framed
-side by side; http_classify.hip:lat_request) against the oracle.
+side by side; http_lat.h:lat_request) against the oracle.
 
 Calls of at most 64 requests take it (engine_state.h kLatencyMax): every workload
 below is cut into calls of 1..64 requests and each answer must equal the
