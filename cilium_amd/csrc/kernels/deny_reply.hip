@@ -18,9 +18,10 @@
 //    list (ballot + prefix; one atomic per workgroup step), so that the walks
 //    below run in full waves and not in one lane of 64.
 // 2. deny_kafka_kernel<false>: one lane per list entry decodes its request as
-//    kafka_response.cc's Decode does (kresp::Decode restated over the device's
-//    byte cursor, CRC included: a mismatch stops a message set without
-//    draining it, and the next partition id is then read from inside the set)
+//    kafka_response.cc's Decode does (kresp::Decode restated on the wire
+//    decoder and message set of kafka_wire.h over the device's byte cursor,
+//    CRC included: a mismatch stops a message set without draining it, and
+//    the next partition id is then read from inside the set)
 //    and counts the reply's bytes; any decode error gives length 0.  Then an
 //    exclusive sum of len[] into off[] (hipcub::DeviceScan).
 // 3. deny_fixed_write_kernel writes the templates and the two totals; the
@@ -35,7 +36,7 @@
 
 #include "../deny_templates.h"
 #include "../device_tables.h"
-#include "kafka_dec.h"
+#include "kafka_wire.h"
 #include "launch.h"
 
 namespace l7 {
@@ -49,94 +50,15 @@ constexpr int16_t kErrTopicAuthorizationFailed = 29;  // proto/errors.go:37
 // wrap-around: the ListOffsets v1+ timestamp (messages.go:1996)
 constexpr int64_t kZeroTimeMillis = -6795364578871LL;
 
-// ---------------- the request decoder (kafka_response.cc's Dec) ----------------
-// over a bytes.Buffer: short reads are errors, errors are sticky
-struct RDec {
-    const uint8_t *b;
-    uint32_t pos, end;
-    bool err;
-    Cur *c;
+// The request decoder is kafka_wire.h's KD over the chunk cursor (CurRd), which
+// reads as kafka_response.cc's Dec does: short reads are errors, errors are
+// sticky.  A message set is read for its effect on the position and on errors,
+// as kafka_response.cc's SkipMessageSet (kd_message_set): a compressed message
+// needs no inflate, since its inner set changes nothing the reply echoes, and
+// the walk leaves the set there.
+struct DenySetHooks : CurCrc {
+    static constexpr bool kLeaveAtPacked = true;
 };
-__device__ __forceinline__ uint64_t rd_int(RDec &d, uint32_t n) {
-    if (d.err) return 0;
-    if (d.end - d.pos < n) { d.err = true; d.pos = d.end; return 0; }
-    const uint64_t v = be_load(*d.c, d.b + d.pos, (int)n);
-    d.pos += n;
-    return v;
-}
-__device__ __forceinline__ void rd_skip(RDec &d, uint32_t n) {
-    if (d.err) return;
-    if (d.end - d.pos < n) { d.err = true; d.pos = d.end; return; }
-    d.pos += n;
-}
-// DecodeString: i16 length, < 1 => ""
-__device__ __forceinline__ void rd_str(RDec &d, uint32_t &off, uint32_t &len) {
-    off = 0; len = 0;
-    const int16_t n = (int16_t)rd_int(d, 2);
-    if (d.err || n < 1) return;
-    if (d.end - d.pos < (uint32_t)n) { d.err = true; d.pos = d.end; return; }
-    off = d.pos; len = (uint32_t)n;
-    d.pos += (uint32_t)n;
-}
-// DecodeArrayLen
-__device__ __forceinline__ int32_t rd_arrlen(RDec &d, bool nullable, bool &bad) {
-    const int32_t l = (int32_t)rd_int(d, 4);
-    bad = false;
-    if (l < 0) {
-        if (nullable) return -1;
-        bad = true;
-        return 0;
-    }
-    if ((uint32_t)l > kMaxParseBuf) { bad = true; return 0; }
-    return l;
-}
-// DecodeBytes, dropped
-__device__ __forceinline__ void rd_bytes(RDec &d) {
-    const int32_t n = (int32_t)rd_int(d, 4);
-    if (d.err || n < 1) return;
-    if ((uint32_t)n > kMaxParseBuf) { d.err = true; return; }
-    rd_skip(d, (uint32_t)n);
-}
-
-// readMessageSet (messages.go:363-494) for its effect on the position and on
-// errors, as kafka_response.cc's SkipMessageSet; 0 ok, -1 error.  A compressed
-// message needs no inflate: its inner set changes nothing the reply echoes.
-// whole: cleared when the walk leaves the set before its end (a CRC mismatch,
-// a compressed or short message).  skip: the size pass found every set of
-// this request read to its end, so the write pass steps over them, CRCs unread.
-__device__ __forceinline__ int rd_message_set(RDec &d, int32_t size, int16_t version, const uint32_t *crctab,
-                                              bool &whole, bool skip) {
-    if (size < 0) return 0;
-    if ((uint32_t)size > kMaxParseBuf) return -1;
-    const uint32_t room = d.end - d.pos;
-    RDec s{d.b, d.pos, d.pos + ((uint32_t)size < room ? (uint32_t)size : room), false, d.c};
-    if (skip) { d.pos = s.end; return 0; }
-    for (;;) {
-        (void)rd_int(s, 8);
-        if (s.err) break;
-        const int32_t msize = (int32_t)rd_int(s, 4);
-        if (s.err || msize <= 0) break;
-        if ((uint32_t)msize > kMaxParseBuf) return -1;
-        const uint32_t at = s.pos;
-        rd_skip(s, (uint32_t)msize);
-        if (s.err) break;
-        if (msize <= 4) break;
-        const uint32_t crc = (uint32_t)be_load(*d.c, d.b + at, 4);
-        if (crc != crc32_ieee(crctab, *d.c, d.b + at + 4, (uint32_t)msize - 4)) break;  // stop, no drain
-        RDec m{d.b, at + 4, at + (uint32_t)msize, false, d.c};
-        (void)rd_int(m, 1);
-        const int8_t attr = (int8_t)rd_int(m, 1);
-        if (version >= 1) (void)rd_int(m, 8);
-        if ((attr & 3) == 3) break;
-        rd_bytes(m);
-        rd_bytes(m);
-        if (m.err) return -1;
-        if ((attr & 3) != 0) break;
-    }
-    whole = whole && s.pos == s.end;
-    d.pos = s.pos;
-    return 0;
-}
 
 // ---------------- the reply emitters ----------------
 // what the size pass runs the walk with: the bytes, counted
@@ -220,49 +142,63 @@ __device__ __forceinline__ void emit_partition(E &e, int kind, int16_t v, int32_
 // error): whatever was emitted until then is void -- the size pass answers
 // length 0, and the write pass only walks requests the size pass accepted.
 // `total`: the reply's length (its size word is total - 4; the size pass gives 0).
-// whole / skip: rd_message_set's.
+// whole: cleared when the walk leaves a message set before its end (a CRC
+// mismatch, a compressed or short message).  skip: the size pass found every
+// set of this request read to its end, so the write pass steps over them, CRCs
+// unread.
 template <class E>
 __device__ __forceinline__ bool reply_walk(const uint8_t *b, uint32_t len, const uint32_t *crctab, uint32_t total,
                                            E &e, bool &whole, bool skip) {
     if (len < 12) return false;
     Cur cur;
     cur.line = ~(uintptr_t)0;
-    const int32_t size = (int32_t)be_load(cur, b, 4);
+    CurRd r{b, &cur};
+    const int32_t size = (int32_t)r.be(0, 4);
     if (size <= 0 || (uint64_t)(uint32_t)size + 4 > len || (uint64_t)(uint32_t)size + 4 > kMaxParseBuf ||
         (uint32_t)size + 4 < 12)
         return false;
-    RDec d{b, 4, (uint32_t)size + 4, false, &cur};
-    const int kind = (int16_t)rd_int(d, 2);
-    const int16_t v = (int16_t)rd_int(d, 2);
-    const uint32_t corr = (uint32_t)rd_int(d, 4);
+    KD<CurRd> d{&r, 4, (uint32_t)size + 4, -1, 0};
+    const int kind = (int16_t)kd_int(d, 2);
+    const int16_t v = (int16_t)kd_int(d, 2);
+    const uint32_t corr = (uint32_t)kd_int(d, 4);
     if (!(kind == 0 || kind == 1 || kind == 2 || kind == 3 || kind == 8 || kind == 9 || kind == 10))
         return false;  // request == nil: "unsupported request API key"
     uint32_t o, l;
-    rd_str(d, o, l);  // ClientID
+    kd_string(d, o, l);  // ClientID
     e.put(total - 4, 4);
     e.put(corr, 4);
-    bool bad = false;
+    bool bad = false, packed = false;  // (packed: kd_message_set's zflag, not used here)
+    DenySetHooks h{{crctab, r}};
     int32_t nt = 0, np = 0;
     switch (kind) {
     case 0:  // Produce (messages.go:1591-1647) -> ProduceResp.Bytes (:1716)
-        if (v >= 3) rd_str(d, o, l);
-        rd_skip(d, 6);
-        nt = rd_arrlen(d, false, bad);
+        if (v >= 3) kd_string(d, o, l);
+        kd_skip(d, 6);
+        nt = kd_arraylen(d, false, bad);
         if (bad) return false;
         e.put((uint32_t)nt, 4);
         for (int32_t t = 0; t < nt; t++) {
-            rd_str(d, o, l);
+            kd_string(d, o, l);
             if (d.err) return false;
-            np = rd_arrlen(d, false, bad);
+            np = kd_arraylen(d, false, bad);
             if (bad) return false;
             e.put(l, 2);
             e.copy(b + o, l);
             e.put((uint32_t)np, 4);
             for (int32_t p = 0; p < np; p++) {
-                const int32_t id = (int32_t)rd_int(d, 4);
-                const int32_t ss = (int32_t)rd_int(d, 4);
+                const int32_t id = (int32_t)kd_int(d, 4);
+                const int32_t ss = (int32_t)kd_int(d, 4);
                 if (d.err) return false;
-                if (rd_message_set(d, ss, v, crctab, whole, skip) < 0) return false;
+                if (ss > (int32_t)kMaxParseBuf) return false;
+                // the set's bytes: min(size, room); read whole when the walk advances by exactly that
+                const uint32_t room = d.end - d.pos, at = d.pos;
+                const uint32_t want = ss < 0 ? 0u : (uint32_t)ss < room ? (uint32_t)ss : room;
+                if (skip) {
+                    d.pos += want;
+                } else {
+                    if (kd_message_set(r, d.pos, d.end, ss, v, packed, h) < 0) return false;
+                    whole = whole && d.pos - at == want;
+                }
                 emit_partition(e, 0, v, id);
             }
         }
@@ -273,42 +209,42 @@ __device__ __forceinline__ bool reply_walk(const uint8_t *b, uint32_t len, const
     case 8:  // OffsetCommit (:1173-1228) -> OffsetCommitResp.Bytes (:1342)
     case 9:  // OffsetFetch (:1389-1430) -> OffsetFetchResp.Bytes (:1531)
         if (kind == 1) {
-            rd_skip(d, 12);
-            if (v >= 3) rd_skip(d, 4);
-            if (v >= 4) rd_skip(d, 1);
+            kd_skip(d, 12);
+            if (v >= 3) kd_skip(d, 4);
+            if (v >= 4) kd_skip(d, 1);
             if (v >= 1) e.zeros(4);
         } else if (kind == 2) {
-            rd_skip(d, 4);
-            if (v >= 2) { rd_skip(d, 1); e.zeros(4); }
+            kd_skip(d, 4);
+            if (v >= 2) { kd_skip(d, 1); e.zeros(4); }
         } else if (kind == 8) {
-            rd_str(d, o, l);
-            if (v >= 1) { rd_skip(d, 4); rd_str(d, o, l); }
-            if (v >= 2) rd_skip(d, 8);
+            kd_string(d, o, l);
+            if (v >= 1) { kd_skip(d, 4); kd_string(d, o, l); }
+            if (v >= 2) kd_skip(d, 8);
             if (v >= 3) e.zeros(4);
         } else {
-            rd_str(d, o, l);
+            kd_string(d, o, l);
             if (v >= 3) e.zeros(4);
         }
-        nt = rd_arrlen(d, kind == 9, bad);
+        nt = kd_arraylen(d, kind == 9, bad);
         if (bad) return false;
         e.put((uint32_t)nt, 4);  // (a null OffsetFetch array: -1)
         for (int32_t t = 0; t < nt && !d.err; t++) {
-            rd_str(d, o, l);
-            np = rd_arrlen(d, false, bad);
+            kd_string(d, o, l);
+            np = kd_arraylen(d, false, bad);
             if (bad) return false;
             e.put(l, 2);
             e.copy(b + o, l);
             e.put((uint32_t)np, 4);
             for (int32_t p = 0; p < np && !d.err; p++) {
-                const int32_t id = (int32_t)rd_int(d, 4);
+                const int32_t id = (int32_t)kd_int(d, 4);
                 if (kind == 1) {
-                    rd_skip(d, v >= 5 ? 20 : 12);
+                    kd_skip(d, v >= 5 ? 20 : 12);
                 } else if (kind == 2) {
-                    rd_skip(d, v == 0 ? 12 : 8);
+                    kd_skip(d, v == 0 ? 12 : 8);
                 } else if (kind == 8) {
-                    rd_skip(d, v == 1 ? 16 : 8);
+                    kd_skip(d, v == 1 ? 16 : 8);
                     uint32_t o2, l2;
-                    rd_str(d, o2, l2);
+                    kd_string(d, o2, l2);
                 }
                 emit_partition(e, kind, v, id);
             }
@@ -320,21 +256,21 @@ __device__ __forceinline__ bool reply_walk(const uint8_t *b, uint32_t len, const
         e.zeros(4);              // Brokers: empty, not nil
         if (v >= 2) e.zeros(2);  // ClusterID
         if (v >= 1) e.zeros(4);  // ControllerID
-        nt = rd_arrlen(d, true, bad);
+        nt = kd_arraylen(d, true, bad);
         if (bad) return false;
         e.put((uint32_t)nt, 4);
         for (int32_t t = 0; t < nt && !d.err; t++) {
-            rd_str(d, o, l);
+            kd_string(d, o, l);
             e.put(kErrTopicAuthorizationFailed, 2);
             e.put(l, 2);
             e.copy(b + o, l);
             e.zeros(v >= 1 ? 5 : 4);  // v1+ IsInternal; Partitions: empty, not nil
         }
-        if (v >= 4) rd_skip(d, 1);
+        if (v >= 4) kd_skip(d, 1);
         break;
     default:  // 10: ConsumerMetadata (:1033-1054) -> ConsumerMetadataResp.Bytes (:1117)
-        rd_str(d, o, l);
-        if (v >= 1) rd_skip(d, 1);
+        kd_string(d, o, l);
+        if (v >= 1) kd_skip(d, 1);
         if (v >= 1) e.zeros(4);
         e.put(kErrTopicAuthorizationFailed, 2);
         e.zeros(v >= 1 ? 12 : 10);  // v1+ ErrMsg; CoordinatorID, CoordinatorHost, CoordinatorPort
@@ -426,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void deny_kafka_kernel(Batch B, uint32_t *_
     __shared__ uint32_t wnz[kBlock / 64];
     const uint32_t m = ctl[0];
     if ((uint64_t)blockIdx.x * kBlock >= m) return;  // (the whole workgroup: before the tables' barriers)
-    crc_tables_init(crctab, threadIdx.x);
+    crc_tables_init<kBlock>(crctab, threadIdx.x);
     uint32_t nz = 0;
     for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < m; j += (uint64_t)gridDim.x * kBlock) {
         const uint32_t ent = klist[j];

@@ -11,9 +11,11 @@
 // (engine/kafka_compile.h).  Requests with compressed messages are listed for
 // kafka_inflate_kernel (kafka_inflate.hip), which decodes them.
 //
-// Round 5: the decoders are one template over the byte source (kafka_walk,
-// kd_*), and the two loops that dominate the instruction count take a
-// straight-line path when their input is well formed: a message whose
+// Round 5: the decoders are one template over the byte source (kafka_walk
+// here; KD<R>, kd_* and kd_message_set in kafka_wire.h, shared with the
+// compressed-set and deny-reply kernels), and the two loops that dominate
+// the instruction count take a straight-line path when their input is well
+// formed: a message whose
 // header, key and value lie inside it and its set is read from one 36-byte
 // window (three or four chunk loads issued together, the fields at fixed
 // places), and a fetch / offsets / offset-fetch partition array whose
@@ -27,7 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../device_tables.h"
-#include "kafka_dec.h"
+#include "kafka_wire.h"
 #include "launch.h"
 
 namespace l7 {
@@ -36,24 +38,6 @@ namespace {
 
 constexpr int kBlock = 256;  // threads per workgroup: the CRC tables are shared by its waves
 
-
-// 4 bytes at p as a little-endian word through the lane's chunk cursor
-__device__ __forceinline__ uint32_t le_load4(Cur &c, const uint8_t *p) {
-    const uintptr_t a = (uintptr_t)p;
-    const uint32_t k = (uint32_t)(a & 15);
-    if (k <= 12) {
-        cur_fill(c, a);
-        const uint32_t w0 = c.w0, w1 = c.w1, w2 = c.w2, w3 = c.w3;
-        const uint32_t i = k >> 2;
-        const uint32_t lo = i == 0 ? w0 : i == 1 ? w1 : i == 2 ? w2 : w3;
-        const uint32_t hi = i == 0 ? w1 : i == 1 ? w2 : i == 2 ? w3 : 0u;
-        return __builtin_amdgcn_alignbyte(hi, lo, k & 3);
-    }
-    uint32_t v = 0;
-    for (int i = 0; i < 4; i++) v |= cur_byte(c, p + i) << (8 * i);
-    return v;
-}
-__device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_amdgcn_perm(0, x, 0x00010203u); }
 
 // The request in HBM through the lane's 16-byte chunk cursor.
 struct GRd {
@@ -119,7 +103,7 @@ struct GRd {
     __device__ __forceinline__ uint64_t be(uint32_t pos, int n) {
         const uint32_t o = pos - span;
         if (n <= 4 && o <= 60u) {
-            const uint32_t v = bswap(slot_le4(o));
+            const uint32_t v = bswap32(slot_le4(o));
             return n == 4 ? v : v >> (32 - 8 * n);
         }
         return be_load(cur, b + pos, n);
@@ -175,171 +159,8 @@ struct GRd {
     }
     // big-endian 4 bytes at byte o (o + 4 <= 64) of the slot, which holds the window block win9 left
     // there: a field past the 36 bytes win9 returns, without a round trip
-    __device__ __forceinline__ uint32_t win_be4(uint32_t o) { return bswap(slot_le4(o)); }
+    __device__ __forceinline__ uint32_t win_be4(uint32_t o) { return bswap32(slot_le4(o)); }
 };
-
-// ---------------- io.ReadFull / LimitReader decoding over a byte source ----------------
-template <class R>
-struct KD {
-    R *r;
-    uint32_t pos, end;
-    int32_t limit;  // LimitReader remaining, -1 = none
-    int err;        // 0 ok, 1 EOF, 2 ErrUnexpectedEOF, 3 other
-};
-template <class R>
-__device__ __forceinline__ uint32_t kd_read(KD<R> &d, uint32_t n) {
-    const uint32_t at = d.pos;
-    if (n == 0) return at;
-    uint32_t a = d.end - d.pos;
-    if (d.limit >= 0 && (uint32_t)d.limit < a) a = (uint32_t)d.limit;
-    if (a == 0) { d.err = 1; return at; }
-    const uint32_t take = a < n ? a : n;
-    d.pos += take;
-    if (d.limit >= 0) d.limit -= (int32_t)take;
-    if (take < n) d.err = 2;
-    return at;
-}
-template <class R>
-__device__ __forceinline__ int64_t kd_int(KD<R> &d, int n) {
-    if (d.err) return 0;
-    const uint32_t at = kd_read(d, (uint32_t)n);
-    if (d.err) return 0;
-    const uint64_t v = d.r->be(at, n);
-    return n == 1 ? (int64_t)(int8_t)v : n == 2 ? (int64_t)(int16_t)v : n == 4 ? (int64_t)(int32_t)v : (int64_t)v;
-}
-template <class R>
-__device__ __forceinline__ void kd_skip(KD<R> &d, int n) {
-    if (d.err) return;
-    kd_read(d, (uint32_t)n);
-}
-template <class R>
-__device__ __forceinline__ void kd_string(KD<R> &d, uint32_t &off, uint32_t &len) {  // DecodeString; len < 1 => ""
-    off = 0; len = 0;
-    if (d.err) return;
-    const int16_t sl = (int16_t)kd_int(d, 2);
-    if (d.err || sl < 1) return;
-    const uint32_t at = kd_read(d, (uint32_t)sl);
-    if (d.err) return;
-    off = at; len = (uint32_t)sl;
-}
-template <class R>
-__device__ __forceinline__ int32_t kd_arraylen(KD<R> &d, bool nullable, bool &bad) {  // DecodeArrayLen
-    const int32_t l = (int32_t)kd_int(d, 4);
-    bad = false;
-    if (l < 0) { if (nullable) return -1; bad = true; return 0; }
-    if ((uint32_t)l > kMaxParseBuf) { bad = true; return 0; }
-    return l;
-}
-// np fixed-size entries whose fields are all skipped: passed in one step when
-// they all lie inside the input (the per-field loop then cannot fail)
-template <class R>
-__device__ __forceinline__ bool kd_bulk(KD<R> &d, int32_t np, uint32_t esize) {
-    if (d.err || np < 0) return false;
-    uint32_t a = d.end - d.pos;
-    if (d.limit >= 0 && (uint32_t)d.limit < a) a = (uint32_t)d.limit;
-    const uint64_t need = (uint64_t)(uint32_t)np * esize;
-    if (need > a) return false;
-    d.pos += (uint32_t)need;
-    if (d.limit >= 0) d.limit -= (int32_t)need;
-    return true;
-}
-template <class R>
-__device__ __forceinline__ void kd_bytes(KD<R> &d) {
-    if (d.err) return;
-    const int32_t sl = (int32_t)kd_int(d, 4);
-    if (d.err || sl < 1) return;
-    if ((uint32_t)sl > kMaxParseBuf) { d.err = 3; return; }
-    kd_read(d, (uint32_t)sl);
-}
-
-// readMessageSet (messages.go:363-494) on the shared position; 0 ok, -1 error.
-// h.msg(pos, len, stored) answers whether the CRC of the message's bytes
-// [pos, pos + len) equals stored; false stops the set without draining it.
-template <class R, class H>
-__device__ __forceinline__ int kd_message_set(R &r, uint32_t &pos, uint32_t end, int32_t size, int16_t version,
-                                              bool &zflag, H &h) {
-    if (size < 0) return 0;
-    if ((uint32_t)size > kMaxParseBuf) return -1;
-    KD<R> dec{&r, pos, end, size, 0};
-    int rc = 0;
-    if constexpr (R::kWin) {
-        // Messages whose header, key and value all lie inside the message and
-        // the set take this path: one 36-byte window read per message (offset,
-        // size, CRC, magic, attributes, [timestamp,] key length and, with no
-        // key, value length), the fields at fixed places.  It takes exactly the
-        // steps of the loop below and commits a message only when every one of
-        // them succeeds; anything else goes to that loop, from the same message.
-        const uint32_t hmin = version >= 1 ? 22u : 14u;  // crc magic attr [ts] klen vlen
-        for (;;) {
-            uint32_t avail = dec.end - dec.pos;
-            if ((uint32_t)dec.limit < avail) avail = (uint32_t)dec.limit;
-            if (avail < 12 + hmin) break;
-            uint32_t x[9];
-            r.win9(dec.pos, x);
-            const uint32_t msize = bswap(x[2]);
-            if ((int32_t)msize < (int32_t)hmin || 12 + msize > avail) break;
-            const uint32_t at = dec.pos + 12;
-            const uint32_t crc = bswap(x[3]);
-            const uint32_t attr = (x[4] >> 8) & 0xFF;
-            const int32_t klen = (int32_t)bswap(version >= 1 ? __builtin_amdgcn_alignbyte(x[7], x[6], 2)
-                                                             : __builtin_amdgcn_alignbyte(x[5], x[4], 2));
-            const uint32_t ko = at + (version >= 1 ? 14u : 6u);  // key length field
-            uint32_t vo = ko + 4;
-            int32_t vlen;
-            if (klen < 1) {
-                vlen = (int32_t)bswap(version >= 1 ? __builtin_amdgcn_alignbyte(x[8], x[7], 2)
-                                                   : __builtin_amdgcn_alignbyte(x[6], x[5], 2));
-            } else {
-                if ((uint32_t)klen > msize || vo + (uint32_t)klen + 4 > at + msize) break;
-                vo += (uint32_t)klen;
-                // from the window in the slot when it holds the field (short
-                // keys), else through the cursor, kept on byte at + 4's chunk
-                // where the CRC starts (crc_head hashes it without a round trip)
-                const uint32_t o = vo - r.span;
-                if (o <= 60u) {
-                    vlen = (int32_t)r.win_be4(o);
-                } else {
-                    const Cur keep = r.cur;
-                    vlen = (int32_t)r.be(vo, 4);
-                    r.cur = keep;
-                }
-            }
-            if (vlen >= 1 && ((uint32_t)vlen > msize || vo + 4 + (uint32_t)vlen > at + msize)) break;
-            // committed: the message is read whole
-            dec.pos = at + msize;
-            dec.limit -= (int32_t)(12 + msize);
-            if (!h.msg_win(at + 4, msize - 4, crc)) { pos = dec.pos; return 0; }  // stop, no drain
-            if ((attr & 3) == 3) { pos = dec.pos; return 0; }
-            if (attr & 3) zflag = true;
-        }
-    }
-    for (;;) {
-        kd_skip(dec, 8);
-        if (dec.err) break;
-        const int32_t msize = (int32_t)kd_int(dec, 4);
-        if (dec.err || msize <= 0) break;
-        if ((uint32_t)msize > kMaxParseBuf) { rc = -1; break; }
-        const uint32_t at = kd_read(dec, (uint32_t)msize);
-        if (dec.err) break;
-        KD<R> md{&r, at, at + (uint32_t)msize, -1, 0};
-        const uint32_t crc = (uint32_t)kd_int(md, 4);
-        if (msize <= 4) break;
-        if (!h.msg(at + 4, (uint32_t)msize - 4, crc)) break;  // stop, no drain
-        kd_skip(md, 1);
-        const int8_t attr = (int8_t)kd_int(md, 1);
-        if (version >= 1) kd_skip(md, 8);
-        const int codec = attr & 3;
-        if (codec == 3) break;  // `return nil, err` with err == nil
-        kd_bytes(md);
-        kd_bytes(md);
-        if (md.err) { rc = -1; break; }
-        // gzip / snappy: decoded (and its set read) by kafka_inflate_kernel;
-        // the walk goes on, since a successful decode changes nothing here
-        if (codec != 0) zflag = true;
-    }
-    pos = dec.pos;
-    return rc;
-}
 
 __device__ __forceinline__ bool is_topic_api_key(int k) {
     // 0 1 2 3 4 5 6 8 9 19 20 21 23 24 27 28 34 35 37
@@ -607,6 +428,7 @@ struct TopicLog {
 };
 template <class L>
 struct ExactHooks {
+    static constexpr bool kLeaveAtPacked = false;  // (kd_message_set: listed for kafka_inflate_kernel)
     const KafkaTables &T;
     int32_t rsi;  // the connection's rule set, T.rulesets[rsi]: its address is formed at each use (the index is
                   // one register across the walk, the address two)
@@ -679,7 +501,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves, 
     __shared__ __attribute__((aligned(16))) uint8_t crcstage[kBlock / 64][4096];
     // (the wave's index as a scalar: the slot's address stays in scalar registers, not in a VGPR per lane)
     uint8_t *stage = crcstage[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
-    crc_tables_init(crctab, threadIdx.x);
+    crc_tables_init<kBlock>(crctab, threadIdx.x);
     // (L7_KAFKA_CLASSES length classes, class c at sel + c * n, sel_count[c] entries each)
     constexpr int kCls = L7_KAFKA_CLASSES;
     uint32_t kc[kCls] = {n};

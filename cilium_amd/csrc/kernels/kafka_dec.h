@@ -1,9 +1,7 @@
-// Lane-serial Kafka wire decoding helpers shared by the classification kernel
-// (kafka_classify.hip) and the compressed-set kernel (kafka_inflate.hip):
-// the per-lane 16-byte chunk cursor, io.ReadFull / LimitReader reads
-// (vendor/github.com/optiopay/kafka/proto/serialization.go:19-203), big-endian
-// fields and CRC32-IEEE (hash/crc32.ChecksumIEEE, slicing-by-8 LDS tables).
-// Product code.
+// What the Kafka kernels read bytes with, below the wire decoder (kafka_wire.h):
+// the per-lane 16-byte chunk cursor with its big- and little-endian field
+// loads, and CRC32-IEEE (hash/crc32.ChecksumIEEE, slicing-by-8 LDS tables),
+// through the cursor or staged through LDS.  Product code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,21 +14,22 @@ namespace l7 {
 namespace {
 
 constexpr uint32_t kMaxParseBuf = 6553500;
-constexpr int kCrcSlices = 8;
 constexpr int kCrcTables = 8;  // slicing-by-8: T_k[b] = the register after byte b and k zero bytes
-// The tables of one workgroup: thread t < 256 fills entry t of each.
+// The tables of one workgroup of kThreads threads: thread t fills entries
+// t, t + kThreads, ... of each.  (Every thread of the workgroup calls it.)
+template <int kThreads>
 __device__ __forceinline__ void crc_tables_init(uint32_t *tab, uint32_t t) {
-    if (t < 256) {
-        uint32_t c = t;
+    for (uint32_t e = t; e < 256; e += kThreads) {
+        uint32_t c = e;
         for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-        tab[t] = c;
+        tab[e] = c;
     }
     __syncthreads();
-    if (t < 256) {
-        uint32_t v = tab[t];
+    for (uint32_t e = t; e < 256; e += kThreads) {
+        uint32_t v = tab[e];
         for (int k = 1; k < kCrcTables; k++) {
-            v = (v >> 8) ^ tab[v & 0xFF];  // T_k[t]
-            tab[k * 256 + t] = v;
+            v = (v >> 8) ^ tab[v & 0xFF];  // T_k[e]
+            tab[k * 256 + e] = v;
         }
     }
     __syncthreads();
@@ -77,30 +76,25 @@ __device__ __forceinline__ uint32_t cur_byte(Cur &c, const uint8_t *p) {
     return (cur_word(c, k) >> ((k & 3) * 8)) & 0xFFu;
 }
 
-struct KDec {
-    const uint8_t *b;
-    uint32_t pos, end;
-    int32_t limit;  // LimitReader remaining, -1 = none (a set is at most kMaxParseBuf)
-    int err;        // 0 ok, 1 EOF, 2 ErrUnexpectedEOF, 3 other
-    Cur *c;
-};
-
-__device__ __forceinline__ uint32_t kavail(const KDec &d) {
-    uint32_t a = d.end - d.pos;
-    if (d.limit >= 0 && (uint32_t)d.limit < a) a = (uint32_t)d.limit;
-    return a;
+// little-endian bytes k .. k+3 of the cursor's chunk (k <= 12)
+__device__ __forceinline__ uint32_t cur_word_at(const Cur &c, uint32_t k) {
+    const uint32_t w0 = c.w0, w1 = c.w1, w2 = c.w2, w3 = c.w3;
+    const uint32_t i = k >> 2;
+    const uint32_t lo = i == 0 ? w0 : i == 1 ? w1 : i == 2 ? w2 : w3;
+    const uint32_t hi = i == 0 ? w1 : i == 1 ? w2 : i == 2 ? w3 : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, k & 3);
 }
-// io.ReadFull(r, buf[:n]); returns start offset, sets d.err on a short read
-__device__ __forceinline__ uint32_t kread(KDec &d, uint32_t n) {
-    uint32_t at = d.pos;
-    if (n == 0) return at;
-    uint32_t a = kavail(d);
-    if (a == 0) { d.err = 1; return at; }
-    uint32_t take = a < n ? a : n;
-    d.pos += take;
-    if (d.limit >= 0) d.limit -= (int32_t)take;
-    if (take < n) d.err = 2;
-    return at;
+// 4 bytes at p as a little-endian word
+__device__ __forceinline__ uint32_t le_load4(Cur &c, const uint8_t *p) {
+    const uintptr_t a = (uintptr_t)p;
+    const uint32_t k = (uint32_t)(a & 15);
+    if (k <= 12) {
+        cur_fill(c, a);
+        return cur_word_at(c, k);
+    }
+    uint32_t v = 0;
+    for (int i = 0; i < 4; i++) v |= cur_byte(c, p + i) << (8 * i);
+    return v;
 }
 // Big-endian n-byte field (n = 1, 2, 4 or 8).  A field inside the cached
 // 16-byte chunk is cut out of two adjacent words (v_alignbyte) and byte-
@@ -111,54 +105,13 @@ __device__ __forceinline__ uint64_t be_load(Cur &c, const uint8_t *p, int n) {
     const uint32_t k = (uint32_t)(a & 15);
     if (n <= 4 && k + (uint32_t)n <= 16) {
         cur_fill(c, a);
-        const uint32_t w0 = c.w0, w1 = c.w1, w2 = c.w2, w3 = c.w3;
-        const uint32_t i = k >> 2;
-        const uint32_t lo = i == 0 ? w0 : i == 1 ? w1 : i == 2 ? w2 : w3;
-        const uint32_t hi = i == 0 ? w1 : i == 1 ? w2 : i == 2 ? w3 : 0u;
-        const uint32_t v = bswap32(__builtin_amdgcn_alignbyte(hi, lo, k & 3));  // bytes k..k+3, big-endian
+        const uint32_t v = bswap32(cur_word_at(c, k));  // bytes k..k+3, big-endian
         return n == 4 ? v : v >> (32 - 8 * n);
     }
     if (n == 8) return (be_load(c, p, 4) << 32) | be_load(c, p + 4, 4);
     uint64_t v = 0;
     for (int i = 0; i < n; i++) v = (v << 8) | cur_byte(c, p + i);
     return v;
-}
-__device__ __forceinline__ int64_t dec_int(KDec &d, int n) {
-    if (d.err) return 0;
-    uint32_t at = kread(d, (uint32_t)n);
-    if (d.err) return 0;
-    uint64_t v = be_load(*d.c, d.b + at, n);
-    return n == 1 ? (int64_t)(int8_t)v : n == 2 ? (int64_t)(int16_t)v : n == 4 ? (int64_t)(int32_t)v : (int64_t)v;
-}
-// A field whose value is not needed: only the read (and its errors) matter.
-__device__ __forceinline__ void dec_skip(KDec &d, int n) {
-    if (d.err) return;
-    kread(d, (uint32_t)n);
-}
-// DecodeString -> (off, len); len < 1 => ""
-__device__ __forceinline__ void dec_string(KDec &d, uint32_t &off, uint32_t &len) {
-    off = 0; len = 0;
-    if (d.err) return;
-    int16_t sl = (int16_t)dec_int(d, 2);
-    if (d.err || sl < 1) return;
-    uint32_t at = kread(d, (uint32_t)sl);
-    if (d.err) return;
-    off = at; len = (uint32_t)sl;
-}
-// DecodeArrayLen(nullable): -1 null; sets bad on ErrInvalidArrayLen
-__device__ __forceinline__ int32_t dec_arraylen(KDec &d, bool nullable, bool &bad) {
-    int32_t l = (int32_t)dec_int(d, 4);
-    bad = false;
-    if (l < 0) { if (nullable) return -1; bad = true; return 0; }
-    if ((uint32_t)l > kMaxParseBuf) { bad = true; return 0; }
-    return l;
-}
-__device__ __forceinline__ void dec_bytes(KDec &d) {
-    if (d.err) return;
-    int32_t sl = (int32_t)dec_int(d, 4);
-    if (d.err || sl < 1) return;
-    if ((uint32_t)sl > kMaxParseBuf) { d.err = 3; return; }
-    kread(d, (uint32_t)sl);
 }
 
 // CRC32-IEEE (hash/crc32.ChecksumIEEE), slicing-by-8: tab holds 8 LDS tables
@@ -180,9 +133,7 @@ __device__ __forceinline__ uint32_t crc32_ieee(const uint32_t *tab, Cur &cur, co
         for (int j = 0; j < 8; j++) {
             const uint4 &x = v[j >> 1];
             const uint32_t lo = ((j & 1) ? x.z : x.x) ^ c, hi = (j & 1) ? x.w : x.y;
-            c = tab[7 * 256 + (lo & 0xFF)] ^ tab[6 * 256 + ((lo >> 8) & 0xFF)] ^ tab[5 * 256 + ((lo >> 16) & 0xFF)] ^
-                tab[4 * 256 + (lo >> 24)] ^ tab[3 * 256 + (hi & 0xFF)] ^ tab[2 * 256 + ((hi >> 8) & 0xFF)] ^
-                tab[1 * 256 + ((hi >> 16) & 0xFF)] ^ tab[hi >> 24];
+            c = crc_slice8(tab, lo, hi);
         }
     }
     for (; i + 8 <= n; i += 8) {
@@ -191,9 +142,7 @@ __device__ __forceinline__ uint32_t crc32_ieee(const uint32_t *tab, Cur &cur, co
         const uint32_t k = (uint32_t)(a & 15);
         const uint32_t w0 = cur.w0, w1 = cur.w1, w2 = cur.w2, w3 = cur.w3;
         const uint32_t lo = (k ? w2 : w0) ^ c, hi = k ? w3 : w1;
-        c = tab[7 * 256 + (lo & 0xFF)] ^ tab[6 * 256 + ((lo >> 8) & 0xFF)] ^ tab[5 * 256 + ((lo >> 16) & 0xFF)] ^
-            tab[4 * 256 + (lo >> 24)] ^ tab[3 * 256 + (hi & 0xFF)] ^ tab[2 * 256 + ((hi >> 8) & 0xFF)] ^
-            tab[1 * 256 + ((hi >> 16) & 0xFF)] ^ tab[hi >> 24];
+        c = crc_slice8(tab, lo, hi);
     }
     for (; i < n; i++) c = tab[(c ^ cur_byte(cur, p + i)) & 0xFF] ^ (c >> 8);
     return ~c;
@@ -250,14 +199,6 @@ __device__ __forceinline__ uint32_t crc_bytes3(uint32_t tabaddr, uint32_t c, uin
                  : "v"(b0), "v"(b1), "v"(b2)
                  : "memory");
     return (c >> (8 * r)) ^ r0 ^ (r >= 2 ? r1 : 0u) ^ (r >= 3 ? r2 : 0u);
-}
-// little-endian bytes k .. k+3 of the cursor's chunk (k <= 12)
-__device__ __forceinline__ uint32_t cur_word_at(const Cur &c, uint32_t k) {
-    const uint32_t w0 = c.w0, w1 = c.w1, w2 = c.w2, w3 = c.w3;
-    const uint32_t i = k >> 2;
-    const uint32_t lo = i == 0 ? w0 : i == 1 ? w1 : i == 2 ? w2 : w3;
-    const uint32_t hi = i == 0 ? w1 : i == 1 ? w2 : i == 2 ? w3 : 0u;
-    return __builtin_amdgcn_alignbyte(hi, lo, k & 3);
 }
 
 // The same CRC with the bulk loads staged through LDS (kafka_classify): the

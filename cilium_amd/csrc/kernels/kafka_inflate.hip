@@ -18,8 +18,8 @@
 //   - output goes to the workgroup's slice of a decode region in HBM, one
 //     dword store per 4 bytes, as a stack: a nested compressed message is
 //     decoded above its parent's buffer and popped when its set ends;
-//   - inner sets are walked from HBM with the same chunk cursor and slicing-
-//     by-8 CRC as the classifier.
+//   - inner sets are walked from HBM with the wire decoder and message step of
+//     kafka_wire.h over the chunk cursor, and the cursor's slicing-by-8 CRC.
 // Result per listed request: unchanged (every level decoded and parsed),
 // PARSE_ERROR (a decode or inner-set error, as in the reference), or
 // UNSUPPORTED when one nesting path needs more decoded bytes than the
@@ -27,7 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../device_tables.h"
-#include "kafka_dec.h"
+#include "kafka_wire.h"
 #include "launch.h"
 
 namespace l7 {
@@ -53,7 +53,7 @@ struct Huff {
 
 // LDS of one workgroup (one wave)
 struct ZShared {
-    uint32_t crctab[kCrcSlices * 256];
+    uint32_t crctab[kCrcTables * 256];
     uint8_t win[kWin];
     Huff lit, dist, clen;
     uint8_t lens[320];
@@ -445,69 +445,29 @@ __device__ int zset(ZCtx &z, const uint8_t *b, uint32_t &pos, uint32_t end, int3
     uint32_t top = 0;  // first free byte of the region slice
     int rc = 0;
     for (;;) {
-        const uint8_t *fbd = fb[depth];
-        KDec dec{fbd, fpos[depth], fend[depth], flim[depth], 0, &z.cur};
-        bool stop = false, push = false;
-        uint32_t vat = 0, vlen = 0;
-        int codec = 0;
-        dec_skip(dec, 8);
-        int32_t msize = 0;
-        if (dec.err) stop = true;
-        if (!stop) {
-            msize = (int32_t)dec_int(dec, 4);
-            if (dec.err || msize <= 0) stop = true;
-        }
-        if (!stop && (uint32_t)msize > kMaxParseBuf) { rc = -1; break; }
-        uint32_t at = 0;
-        if (!stop) {
-            at = kread(dec, (uint32_t)msize);
-            if (dec.err) stop = true;
-        }
-        if (!stop) {
-            KDec md{fbd, at, at + (uint32_t)msize, -1, 0, &z.cur};
-            const uint32_t crc = (uint32_t)dec_int(md, 4);
-            if (msize <= 4 || crc != crc32_ieee(z.sh->crctab, z.cur, fbd + at + 4, (uint32_t)msize - 4)) {
-                stop = true;  // stop, no drain
-            } else {
-                dec_skip(md, 1);
-                const int8_t attr = (int8_t)dec_int(md, 1);
-                if (version >= 1) dec_skip(md, 8);
-                codec = attr & 3;
-                if (codec == 3) {
-                    stop = true;
-                } else {
-                    dec_bytes(md);
-                    if (codec == 0) {
-                        dec_bytes(md);
-                    } else if (!md.err) {  // the value: where and how long
-                        const int32_t sl = (int32_t)dec_int(md, 4);
-                        if (!md.err && sl >= 1) {
-                            if ((uint32_t)sl > kMaxParseBuf) md.err = 3;
-                            else { vat = kread(md, (uint32_t)sl); if (!md.err) vlen = (uint32_t)sl; }
-                        }
-                    }
-                    if (md.err) { rc = -1; break; }
-                    push = codec != 0;
-                }
-            }
-        }
+        CurRd r{fb[depth], &z.cur};
+        KD<CurRd> dec{&r, fpos[depth], fend[depth], flim[depth], 0};
+        CurCrc h{z.sh->crctab, r};
+        KMsg m;
+        const KMsgStep st = kd_message(dec, version, h, m);
+        if (st == kMsgError) { rc = -1; break; }
         fpos[depth] = dec.pos;
         flim[depth] = dec.limit;
-        if (stop) {
+        if (st == kMsgEnd) {
             if (depth == 0) break;
             top = fbuf[depth];
             depth--;
             continue;
         }
-        if (!push) continue;
+        if (st == kMsgPlain) continue;
         if (depth + 1 == kDepth) { rc = -2; break; }
         // decode the value into the region slice above the parent's bytes
         const uint32_t room = top + 64 <= z.region_bytes ? z.region_bytes - top - 64 : 0;
         const bool region_bound = room < kMaxParseBuf;
         ZOut o{z.region + top, 0, region_bound ? room : kMaxParseBuf, 0, 0, 0xFFFFFFFFu, z.sh};
-        ZIn s{fbd + vat, vlen, 0, 0, 0, {}};
+        ZIn s{r.b + m.vat, m.vlen, 0, 0, 0, {}};
         s.cur.line = ~(uintptr_t)0;
-        const int e = codec == 1 ? zgunzip(s, o) : codec == 2 ? zunsnappy(s, o) : -1;
+        const int e = m.codec == 1 ? zgunzip(s, o) : zunsnappy(s, o);
         if (e) { rc = (e == -3 && region_bound) ? -2 : -1; break; }
         zflush(o);
         z.cur.line = ~(uintptr_t)0;  // the slice may hold a popped level's bytes in the cursor
@@ -527,28 +487,28 @@ __device__ int zset(ZCtx &z, const uint8_t *b, uint32_t &pos, uint32_t end, int3
 // Re-walk a listed Produce request (its structure already parsed without
 // error by kafka_classify_kernel) and decode its compressed messages.
 __device__ int zrequest(ZCtx &z, const uint8_t *b) {
-    Cur &cur = z.cur;
-    const uint32_t rawlen = (uint32_t)be_load(cur, b, 4) + 4;
-    KDec d{b, 0, rawlen, -1, 0, &cur};
+    CurRd r{b, &z.cur};
+    const uint32_t rawlen = (uint32_t)r.be(0, 4) + 4;
+    KD<CurRd> d{&r, 0, rawlen, -1, 0};
     bool bad = false;
-    dec_skip(d, 4); dec_skip(d, 2);
-    const int16_t ver = (int16_t)dec_int(d, 2);
-    dec_skip(d, 4);
+    kd_skip(d, 4); kd_skip(d, 2);
+    const int16_t ver = (int16_t)kd_int(d, 2);
+    kd_skip(d, 4);
     uint32_t o, l;
-    dec_string(d, o, l);
-    if (ver >= 3) dec_string(d, o, l);
-    dec_skip(d, 2); dec_skip(d, 4);
-    const int32_t nt = dec_arraylen(d, false, bad);
+    kd_string(d, o, l);
+    if (ver >= 3) kd_string(d, o, l);
+    kd_skip(d, 2); kd_skip(d, 4);
+    const int32_t nt = kd_arraylen(d, false, bad);
     if (bad || d.err) return 0;
     for (int32_t t = 0; t < nt; t++) {
-        dec_string(d, o, l);
+        kd_string(d, o, l);
         if (d.err) return 0;
-        const int32_t np = dec_arraylen(d, false, bad);
+        const int32_t np = kd_arraylen(d, false, bad);
         if (bad) return 0;
         for (int32_t p = 0; p < np; p++) {
-            dec_skip(d, 4);
+            kd_skip(d, 4);
             if (d.err) return 0;
-            const int32_t ss = (int32_t)dec_int(d, 4);
+            const int32_t ss = (int32_t)kd_int(d, 4);
             if (d.err) return 0;
             const int rc = zset(z, b, d.pos, d.end, ss, ver);
             if (rc) return rc;
@@ -565,21 +525,7 @@ __global__ __launch_bounds__(64) void kafka_inflate_kernel(Batch B, const uint32
     __shared__ ZShared sh;
     const uint32_t count = *zcount;
     if (blockIdx.x >= count) return;
-    {  // CRC tables, 4 entries per lane
-        for (uint32_t t = threadIdx.x; t < 256; t += 64) {
-            uint32_t c = t;
-            for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-            sh.crctab[t] = c;
-        }
-        __syncthreads();
-        for (int k = 1; k < kCrcSlices; k++) {
-            for (uint32_t t = threadIdx.x; t < 256; t += 64) {
-                const uint32_t prev = sh.crctab[(k - 1) * 256 + t];
-                sh.crctab[k * 256 + t] = (prev >> 8) ^ sh.crctab[prev & 0xFF];
-            }
-            __syncthreads();
-        }
-    }
+    crc_tables_init<64>(sh.crctab, threadIdx.x);
     if (threadIdx.x != 0) return;
     ZCtx z;
     z.sh = &sh;
