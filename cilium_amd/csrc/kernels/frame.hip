@@ -9,9 +9,9 @@
 // (proxylib/r2d2/r2d2parser.go:140-214) and cassandra's 9-byte header plus
 // body length (proxylib/cassandra/cassandraparser.go:171-230).
 //
-// One lane per stream walks it frame by frame and writes each frame's start
-// and the bytes from there to the stream's end (the length a parser is handed,
-// as proxylib hands OnData's joined input): the classifiers then answer each
+// A stream is walked frame by frame, and each frame's start is written with
+// the bytes from there to the stream's end (the length a parser is handed, as
+// proxylib hands OnData's joined input): the classifiers then answer each
 // frame, and their consumed length confirms the walk.  The walk stops where a
 // frame is incomplete or its length cannot be read ahead of parsing it (a
 // chunked HTTP body, a malformed size, a memcached storage line without a byte
@@ -19,11 +19,18 @@
 // frames what follows after the verdict, as the proxylib op loop does.  These
 // are the proposals csrc/proxylib/shim.cc scans on the host (Next*), made on
 // the device for many streams at once.
+//
+// Two kernels share the streams of a call, each skipping the other's:
+// frame_streams_kernel frames the length-prefixed protocols (Kafka, cassandra,
+// memcached binary), one lane per stream: a frame is a header read and an
+// addition; frame_text_kernel frames the line protocols (HTTP, memcached text,
+// r2d2), one wave per stream: a frame's end is searched for, 1 KiB at a time.
 #include <hip/hip_runtime.h>
 
 #include "../device_tables.h"
 #include "gmem.h"
 #include "launch.h"
+#include "text_bytes.h"
 
 namespace l7 {
 
@@ -38,7 +45,7 @@ struct Stream {
     uint4 w;
 };
 
-// byte i of the stream, through a one-block cache: a lane scanning a line
+// byte i of the stream, through a one-block cache: a lane reading a header
 // issues one 16-byte load per block instead of one (dependent) load per byte
 __device__ __forceinline__ uint32_t sbyte(Stream &S, uint64_t i) {
     const uint64_t a = (uint64_t)S.b + i, base = a & ~15ull;
@@ -49,54 +56,6 @@ __device__ __forceinline__ uint32_t sbyte(Stream &S, uint64_t i) {
     const uint32_t k = (uint32_t)(a & 15);
     const uint32_t d = k < 8 ? (k < 4 ? S.w.x : S.w.y) : (k < 12 ? S.w.z : S.w.w);
     return (d >> (8 * (k & 3))) & 0xFF;
-}
-
-// byte i straight from memory (short lines: the memcached token scan, where
-// the block cache's compare and select cost more than the L1 hit they save)
-__device__ __forceinline__ uint32_t dbyte(const Stream &S, uint64_t i) { return S.b[i]; }
-
-__device__ __forceinline__ uint32_t eq16(uint4 w, uint32_t c) {  // bit k: byte k of w == c
-    const uint32_t cc = c * 0x01010101u;
-    auto e = [cc](uint32_t x) {
-        const uint32_t t = x ^ cc;
-        return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
-    };
-    auto nib = [](uint32_t s) { return __builtin_amdgcn_ubfe((s >> 7) * 0x204081u, 21, 4); };
-    return nib(e(w.x)) | nib(e(w.y)) << 4 | nib(e(w.z)) << 8 | nib(e(w.w)) << 12;
-}
-
-// 16-byte loads in flight per step of the CRLF scan (1M HTTP requests in 16k
-// streams: 4 -> 7.6 ms, 8 -> 6.9, 16 -> 6.7; memcached text 9.1, 8.6, 8.7)
-constexpr int kScan = 8;
-
-// first i in [from, S.n) with b[i] == '\r' and b[i + 1] == '\n' (S.n: none),
-// 16 * kScan bytes a step
-__device__ uint64_t find_crlf(Stream &S, uint64_t from) {
-    if (from >= S.n) return S.n;
-    const uint64_t a = (uint64_t)S.b + from;
-    uint64_t base = a & ~15ull;
-    const uint64_t end = (uint64_t)S.b + S.n;
-    uint32_t skip = (uint32_t)(a - base);
-    uint32_t prev_cr = 0;  // the last block ended in '\r'
-    for (; base < end; base += 16 * kScan) {
-        uint4 w[kScan];
-#pragma unroll
-        for (int k = 0; k < kScan; k++)
-            if (base + 16 * k < end) w[k] = gload16(base + 16 * k);
-#pragma unroll
-        for (int k = 0; k < kScan; k++) {
-            const uint64_t bk = base + 16 * k;
-            if (bk >= end) break;
-            uint32_t valid = end - bk >= 16 ? 0xFFFFu : (1u << (uint32_t)(end - bk)) - 1u;
-            valid &= 0xFFFFu << skip;
-            skip = 0;
-            const uint32_t cr = eq16(w[k], '\r') & valid, lf = eq16(w[k], '\n') & valid;
-            const uint32_t hit = ((cr << 1) | prev_cr) & lf;  // LF right after a CR
-            if (hit) return bk - (uint64_t)S.b + __builtin_ctz(hit) - 1;
-            prev_cr = (cr >> 15) & 1;
-        }
-    }
-    return S.n;
 }
 
 // NextKafka: [size int32 BE][size bytes]; size <= 0 or past the stream: stop
@@ -114,154 +73,12 @@ __device__ uint64_t next_mc_binary(Stream &S, uint64_t p) {
     return body + 24 <= S.n - p ? p + 24 + body : 0;
 }
 
-// bytes.Fields' separators (unicode.IsSpace) at s[i], as shim.cc SpaceLen:
-// the width of the space rune there, 0 for none
-__device__ uint32_t space_len(Stream &S, uint64_t i, uint64_t n) {
-    const uint32_t c = dbyte(S, i);
-    if (c == ' ' || (c >= 0x09 && c <= 0x0D)) return 1;
-    if (c < 0xC2 || c > 0xE3 || i + 1 >= n) return 0;
-    const uint32_t c1 = dbyte(S, i + 1);
-    if (c == 0xC2) return (c1 == 0x85 || c1 == 0xA0) ? 2 : 0;
-    if (i + 2 >= n) return 0;
-    const uint32_t c2 = dbyte(S, i + 2);
-    if (c == 0xE1) return (c1 == 0x9A && c2 == 0x80) ? 3 : 0;
-    if (c == 0xE2 && c1 == 0x80) return ((c2 >= 0x80 && c2 <= 0x8A) || c2 == 0xA8 || c2 == 0xA9 || c2 == 0xAF) ? 3 : 0;
-    if (c == 0xE2 && c1 == 0x81) return c2 == 0x9F ? 3 : 0;
-    if (c == 0xE3) return (c1 == 0x80 && c2 == 0x80) ? 3 : 0;
-    return 0;
-}
-
-// NextMcText: the line to "\r\n"; set / add / replace / append / prepend / cas
-// also carry <bytes> + "\r\n" of data (tokens[4], a non-negative decimal)
-__device__ uint64_t next_mc_text(Stream &S, uint64_t p) {
-    const uint64_t lf = find_crlf(S, p);
-    if (lf >= S.n) return 0;
-    // tokens 0 and 4 of the line [p, lf)
-    uint64_t t0 = 0, t0e = 0, t4 = 0, t4e = 0;
-    uint32_t nt = 0;
-    bool in = false;
-    for (uint64_t i = p; i < lf;) {
-        const uint32_t sp = space_len(S, i, lf);
-        if (sp) {
-            if (in) {
-                if (nt == 0) t0e = i;
-                if (nt == 4) t4e = i;
-                nt++;
-            }
-            in = false;
-            i += sp;
-        } else {
-            if (!in) {
-                if (nt == 0) t0 = i;
-                if (nt == 4) t4 = i;
-                in = true;
-            }
-            i++;
-        }
-        if (nt > 4) break;
-    }
-    if (in) {
-        if (nt == 0) t0e = lf;
-        if (nt == 4) t4e = lf;
-        nt++;
-    }
-    uint64_t next = lf + 2;
-    bool storage = false;
-    if (nt >= 1) {
-        const uint64_t k = t0e - t0;
-        auto is = [&](const char *w, uint64_t wl) {
-            if (k != wl) return false;
-            for (uint64_t j = 0; j < wl; j++)
-                if (dbyte(S, t0 + j) != (uint32_t)(uint8_t)w[j]) return false;
-            return true;
-        };
-        storage = is("set", 3) || is("add", 3) || is("replace", 7) || is("append", 6) || is("prepend", 7) || is("cas", 3);
-    }
-    if (storage) {
-        if (nt < 5) return 0;
-        // strtoll(tokens[4]) with the whole token consumed, >= 0
-        uint64_t i = t4;
-        bool neg = false;
-        if (i < t4e && (dbyte(S, i) == '+' || dbyte(S, i) == '-')) {
-            neg = dbyte(S, i) == '-';
-            i++;
-        }
-        if (i >= t4e) return 0;
-        uint64_t v = 0;
-        for (; i < t4e; i++) {
-            const uint32_t d = dbyte(S, i) - '0';
-            if (d > 9) return 0;
-            v = v * 10 + d;
-            if (v > (1ull << 40)) return 0;  // (strtoll saturates; no such frame fits a stream)
-        }
-        if (neg && v) return 0;
-        next += v + 2;
-    }
-    return next <= S.n ? next : 0;
-}
-
-// NextLine (r2d2): to "\r\n"
-__device__ uint64_t next_line(Stream &S, uint64_t p) {
-    const uint64_t lf = find_crlf(S, p);
-    return lf >= S.n ? 0 : lf + 2;
-}
-
-__device__ __forceinline__ uint32_t lower(uint32_t c) { return c - 'A' < 26u ? c + 32 : c; }
-
-// NextHttp: the head to "\r\n\r\n" plus Content-Length (strtoull of the value);
-// a Transfer-Encoding header stops the walk (chunked bodies are framed by the
-// classifier)
-__device__ uint64_t next_http(Stream &S, uint64_t p) {
-    uint64_t ls = find_crlf(S, p);
-    if (ls >= S.n) return 0;
-    ls += 2;
-    uint64_t cl = 0;
-    for (;;) {  // header lines until the empty one
-        const uint64_t le = find_crlf(S, ls);
-        if (le >= S.n) return 0;  // no "\r\n\r\n": incomplete
-        if (le == ls) break;      // the empty line: the head ends at ls + 2
-        // the name is the line up to its first ':'; the two names that matter
-        // hold no ':', so a line names one iff its ':' sits right after it
-        // (no byte-wise colon scan of every header line)
-        auto name_is = [&](const char *w, uint64_t wl) {
-            if (le - ls <= wl || sbyte(S, ls + wl) != ':') return false;
-            for (uint64_t j = 0; j < wl; j++)
-                if (lower(sbyte(S, ls + j)) != (uint32_t)(uint8_t)w[j]) return false;
-            return true;
-        };
-        if (name_is("transfer-encoding", 17)) return 0;
-        if (name_is("content-length", 14)) {  // strtoull: leading spaces, optional sign, digits
-            uint64_t i = ls + 15;
-            while (i < S.n && (sbyte(S, i) == ' ' || (sbyte(S, i) >= 0x09 && sbyte(S, i) <= 0x0D))) i++;
-            bool neg = false;
-            if (i < S.n && (sbyte(S, i) == '+' || sbyte(S, i) == '-')) {
-                neg = sbyte(S, i) == '-';
-                i++;
-            }
-            uint64_t v = 0;
-            bool over = false;
-            for (; i < S.n; i++) {
-                const uint32_t d = sbyte(S, i) - '0';
-                if (d > 9) break;
-                if (v > (~0ull - d) / 10) over = true;
-                v = over ? ~0ull : v * 10 + d;
-            }
-            cl = neg ? 0 - v : v;
-        }
-        ls = le + 2;
-    }
-    const uint64_t head_end = ls + 2;
-    if (cl > S.n - head_end) return 0;
-    return head_end + cl;
-}
-
 // cassandra: 9-byte header, body length at bytes 5..8
 __device__ uint64_t next_cassandra(Stream &S, uint64_t p) {
     if (S.n - p < 9) return 0;
     const uint64_t fl = 9 + (uint64_t)(sbyte(S, p + 5) << 24 | sbyte(S, p + 6) << 16 | sbyte(S, p + 7) << 8 | sbyte(S, p + 8));
     return fl <= S.n - p ? p + fl : 0;
 }
-
 
 // ---------------- text streams (HTTP, memcached text, r2d2): a wave per stream ----------------
 // A window is 1 KiB of the stream's address range, 16-byte aligned: lane l
@@ -270,8 +87,7 @@ __device__ uint64_t next_cassandra(Stream &S, uint64_t p) {
 // byte k belongs to a unicode.IsSpace rune as bytes.Fields reads them).  One
 // load instruction brings the whole window (64 lanes x 16 bytes, coalesced);
 // the CR/LF search is a ballot over the lanes' masks.  The frame walk itself
-// is wave-uniform scalar code that reads those registers with v_readlane, so
-// the wave does the work the one-lane walk did, 64 bytes at a time.
+// is wave-uniform scalar code that reads those registers with v_readlane.
 constexpr uint32_t kWinBytes = 1024;
 
 // Phase timing (experiment builds with -DL7G_FRAME_PHASES only): per wave, the
@@ -318,7 +134,7 @@ __device__ __forceinline__ void twin_masks(TWin &W) {
         vm = (0xFFFFu << lo) & (0xFFFFu >> (16 - hi));
     }
     const uint4 w = W.w;
-    const uint32_t cr = eq16(w, '\r') & vm, lf = eq16(w, '\n') & vm;
+    const uint32_t cr = eq_mask(w, '\r') & vm, lf = eq_mask(w, '\n') & vm;
     uint32_t nlf = (uint32_t)__shfl_down((int)lf, 1) & 1u;  // the next chunk's first byte is '\n'
     if (lane == 63) nlf = 0;                                 // (past the window: the next window decides)
     W.crlf = cr & ((lf >> 1) | (nlf << 15));
@@ -334,7 +150,8 @@ __device__ __forceinline__ void twin_masks(TWin &W) {
         // only a line starting with c / C / t / T can name either: the 18 bytes
         // from such a start (this chunk and the next two lanes') are read only
         // when some lane has one
-        const uint32_t cand = starts & (eq16(w, 'c') | eq16(w, 'C') | eq16(w, 't') | eq16(w, 'T'));
+        const uint32_t cand =
+            starts & (eq_mask(w, 'c') | eq_mask(w, 'C') | eq_mask(w, 't') | eq_mask(w, 'T'));
         uint32_t te = 0, clm = 0;
         if (__ballot(cand != 0)) {
             uint32_t x[12];
@@ -374,10 +191,12 @@ __device__ __forceinline__ void twin_masks(TWin &W) {
         // SWAR compares, and the multi-byte runes from their lead bytes (0xC2,
         // 0xE1-0xE3: never a continuation byte, so a rune start is judged on its
         // own bytes; its end lies before any CR), byte by byte only where a lead
-        // byte is
-        const uint32_t asc = eq16(w, 0x20) | eq16(w, 0x09) | eq16(w, 0x0A) | eq16(w, 0x0B) | eq16(w, 0x0C) |
-                             eq16(w, 0x0D);
-        const uint32_t lead = eq16(w, 0xC2) | eq16(w, 0xE1) | eq16(w, 0xE2) | eq16(w, 0xE3);
+        // byte is.  The rune test is ws_rune_len's (text_bytes.h) written out, here
+        // and in tnext_mc_text: through the call this kernel framed memcached text
+        // slower (profiles/text_bytes/speed_compare.md)
+        const uint32_t asc = eq_mask(w, 0x20) | eq_mask(w, 0x09) | eq_mask(w, 0x0A) | eq_mask(w, 0x0B) |
+                             eq_mask(w, 0x0C) | eq_mask(w, 0x0D);
+        const uint32_t lead = eq_mask(w, 0xC2) | eq_mask(w, 0xE1) | eq_mask(w, 0xE2) | eq_mask(w, 0xE3);
         const uint32_t nx = (uint32_t)__shfl_down((int)w.x, 1);
         const uint32_t nxt = lane == 63 ? 0u : nx & 0xFFFFu;  // the next chunk's first two bytes
         uint32_t s2 = 0, s3 = 0;
@@ -477,16 +296,16 @@ __device__ __forceinline__ uint32_t tword(TWin &W, uint64_t x) {
     return __builtin_amdgcn_alignbyte(hi, lo, r & 3);
 }
 
-// NextHttp on the window (next_http's semantics).  The request line ends at
-// the first CRLF; the head ends at the first "\r\n\r\n" from there (the
-// line-by-line walk's first empty line); a transfer-encoding line start in
-// between stops the walk, and the last content-length line start gives the
-// body length.  The masks of a window's last 32 bytes need bytes past it, so a
-// window vouches for its first 992 bytes (all of them when it holds the
-// stream's end) and the scan goes on from there in the window that starts one
-// chunk earlier (kNextWin): lane 0's line starts take no carry from a previous
-// chunk, so a line starting at byte 992 or 993 is seen only with the CRLF
-// before it in the same window.
+// NextHttp: the head to "\r\n\r\n" plus Content-Length (strtoull of the value).
+// The request line ends at the first CRLF; the head ends at the first
+// "\r\n\r\n" from there (the first empty line); a transfer-encoding line start
+// in between stops the walk (chunked bodies are framed by the classifier), and
+// the last content-length line start gives the body length.  The masks of a
+// window's last 32 bytes need bytes past it, so a window vouches for its first
+// 992 bytes (all of them when it holds the stream's end) and the scan goes on
+// from there in the window that starts one chunk earlier (kNextWin): lane 0's
+// line starts take no carry from a previous chunk, so a line starting at byte
+// 992 or 993 is seen only with the CRLF before it in the same window.
 // bits of lanes [c0, c1] (c0 <= c1 < 64)
 __device__ __forceinline__ uint64_t lanes_between(uint32_t c0, uint32_t c1) {
     const uint64_t hi = c1 >= 63 ? ~0ull : (2ull << c1) - 1;
@@ -579,8 +398,10 @@ __device__ __forceinline__ uint64_t tnext_http(TWin &W, uint64_t p) {
     return head_end + cl;
 }
 
-// NextMcText on the window (next_mc_text's semantics): the tokens of the line
-// from the separator masks when the line lies in one window, else byte by byte
+// NextMcText: the line to "\r\n"; set / add / replace / append / prepend / cas
+// also carry <bytes> + "\r\n" of data (tokens[4], a non-negative decimal:
+// strtoll with the whole token consumed).  Tokens 0 and 4 of the line come from
+// the separator masks when the line lies in one window, else byte by byte
 __device__ __forceinline__ uint64_t tnext_mc_text(TWin &W, uint64_t p) {
     const uint64_t lf = tfind_crlf(W, p);
     if (lf >= W.n) return 0;
@@ -615,7 +436,7 @@ __device__ __forceinline__ uint64_t tnext_mc_text(TWin &W, uint64_t p) {
             }
         }
     } else {
-        // a line over a window: bytes.Fields byte by byte (shim.cc SpaceLen)
+        // a line over a window: bytes.Fields byte by byte (ws_rune_len written out, see twin_masks)
         for (uint64_t i = p; i < lf;) {
             const uint32_t c = tbyte(W, i);
             uint32_t sp = 0;
@@ -690,22 +511,28 @@ __device__ __forceinline__ uint64_t tnext_mc_text(TWin &W, uint64_t p) {
     return next <= W.n ? next : 0;
 }
 
+// A stream of frame_text_kernel's (else frame_streams_kernel's).  memcached: the
+// connection's parser, else the first byte's; only L7G_CONN_MC_BINARY alone is
+// binary (both parser flags set read as text, as the classifier reads them).
 __device__ __forceinline__ bool text_stream(const DevConn &c, uint32_t first) {
     if (c.proto == PROTO_HTTP || c.proto == PROTO_R2D2) return true;
     if (c.proto != PROTO_MEMCACHE) return false;
     const uint32_t mode = c.flags & 3;
-    return mode == 1 || (mode == 0 && first < 0x80);
+    return mode == 0 ? first < 0x80 : mode != 2;
 }
 
 }  // namespace
 
-// 4 waves per SIMD (<= 128 VGPRs; left to itself the compiler takes 130 and
-// 3 waves: 1M HTTP requests in 16k streams 6.24 -> 6.28 ms, memcached text
-// 9.05 -> 8.59 ms).  One lane per stream.  Slots [s * max_frames, (s + 1) * max_frames) of the
-// outputs belong to stream s: frame k starts at frame_off (an arena offset)
-// and is handed frame_len bytes (to the stream's end); conn_out = the
-// stream's connection; slots past nframes[s] get length 0 and connection
-// ~0 (answered UNSUPPORTED by the classifiers, which may run over every slot).
+// The length-prefixed protocols (Kafka, cassandra, memcached binary), one lane
+// per stream; text streams are frame_text_kernel's and skipped here.  Slots
+// [s * max_frames, (s + 1) * max_frames) of the outputs belong to stream s:
+// frame k starts at frame_off (an arena offset) and is handed frame_len bytes
+// (to the stream's end); conn_out = the stream's connection; slots past
+// nframes[s] get length 0 and connection ~0 (answered UNSUPPORTED by the
+// classifiers, which may run over every slot).  Streams out of contract or on
+// an unknown connection get their one slot here, whatever their bytes.
+// waves_per_eu(4) dates from a walk that needed the cap to stay at 128 VGPRs;
+// this one takes 70, and the attribute stays until a measurement says otherwise.
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void frame_streams_kernel(const uint8_t *__restrict__ arena, uint64_t arena_len,
                                                                const uint64_t *__restrict__ s_off,
                                                                const uint32_t *__restrict__ s_len,
@@ -714,7 +541,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
                                                                uint32_t max_frames, uint64_t *__restrict__ frame_off,
                                                                uint32_t *__restrict__ frame_len,
                                                                uint32_t *__restrict__ conn_out,
-                                                               uint32_t *__restrict__ nframes, uint32_t text_waves) {
+                                                               uint32_t *__restrict__ nframes) {
     for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < n; s += gridDim.x * kBlock) {
         const uint64_t so = s_off[s];
         const uint32_t sl = s_len[s];
@@ -724,9 +551,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         if (l7_in_arena(so, sl, arena_len) && sl > 0 && ci < nconns) {
             const DevConn c = conns[ci];
             Stream S{arena + so, sl, ~0ull, make_uint4(0, 0, 0, 0)};
-            uint32_t mode = c.flags & 3;  // memcached: the connection's parser, else the first byte's
-            if (c.proto == PROTO_MEMCACHE && mode == 0) mode = sbyte(S, 0) >= 0x80 ? 2 : 1;
-            if (text_waves && text_stream(c, sbyte(S, 0))) continue;  // frame_text_kernel walks it
+            if (text_stream(c, sbyte(S, 0))) continue;  // frame_text_kernel walks it
             for (uint64_t p = 0; p < S.n && k < max_frames;) {
                 frame_off[slot0 + k] = so + p;
                 frame_len[slot0 + k] = (uint32_t)(S.n - p);
@@ -735,10 +560,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
                 uint64_t q = 0;
                 switch (c.proto) {
                 case PROTO_KAFKA: q = next_kafka(S, p); break;
-                case PROTO_HTTP: q = next_http(S, p); break;
-                case PROTO_R2D2: q = next_line(S, p); break;
                 case PROTO_CASSANDRA: q = next_cassandra(S, p); break;
-                case PROTO_MEMCACHE: q = mode == 2 ? next_mc_binary(S, p) : next_mc_text(S, p); break;
+                case PROTO_MEMCACHE: q = next_mc_binary(S, p); break;  // (its text streams were skipped)
                 default: break;
                 }
                 if (q <= p) break;
@@ -759,9 +582,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     }
 }
 
-
-// The text streams (HTTP, memcached text, r2d2), a wave per stream: the same
-// frames as frame_streams_kernel's one-lane walk, whose other streams it skips.
+// The text streams (HTTP, memcached text, r2d2), a wave per stream; every other
+// stream is frame_streams_kernel's and skipped here.
 constexpr int kTBlock = 256;
 __global__ __launch_bounds__(kTBlock) void frame_text_kernel(const uint8_t *__restrict__ arena, uint64_t arena_len,
                                                              const uint64_t *__restrict__ s_off,
@@ -853,7 +675,7 @@ hipError_t LaunchFrameStreams(const uint8_t *arena, uint64_t arena_len, const ui
     if (n == 0) return hipSuccess;
     const uint32_t blocks = min((n + kBlock - 1) / kBlock, 65536u);
     hipLaunchKernelGGL(frame_streams_kernel, dim3(blocks), dim3(kBlock), 0, stream, arena, arena_len, s_off, s_len,
-                       s_conn, n, conns, nconns, max_frames, frame_off, frame_len, conn_out, nframes, 1u);
+                       s_conn, n, conns, nconns, max_frames, frame_off, frame_len, conn_out, nframes);
     const uint32_t tblocks = min((n + kTBlock / 64 - 1) / (kTBlock / 64), 65536u);
     hipLaunchKernelGGL(frame_text_kernel, dim3(tblocks), dim3(kTBlock), 0, stream, arena, arena_len, s_off, s_len,
                        s_conn, n, conns, nconns, max_frames, frame_off, frame_len, conn_out, nframes);

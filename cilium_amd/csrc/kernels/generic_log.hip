@@ -32,6 +32,7 @@
 #include "cass_session.h"
 #include "gmem.h"
 #include "launch.h"
+#include "text_bytes.h"
 
 namespace l7 {
 
@@ -40,34 +41,10 @@ namespace {
 constexpr int kBlock = 256;
 constexpr uint32_t kNoTok = ~0u;
 
-// 16-byte aligned register window over one request
-struct Reader {
-    const uint8_t *b;
-    uint64_t base;
-    uint32_t w0, w1, w2, w3;
-};
-__device__ __forceinline__ uint32_t rd(Reader &r, uint32_t i) {
-    const uint64_t a = (uint64_t)(r.b + i);
-    const uint64_t base = a & ~(uint64_t)15;
-    if (base != r.base) {
-        const uint4 v = gload16(base);  // global, not flat (gmem.h)
-        r.w0 = v.x; r.w1 = v.y; r.w2 = v.z; r.w3 = v.w;
-        r.base = base;
-    }
-    const uint32_t k = (uint32_t)(a >> 2) & 3;
-    const uint32_t w = k == 0 ? r.w0 : k == 1 ? r.w1 : k == 2 ? r.w2 : r.w3;
-    return (w >> ((a & 3) * 8)) & 0xFF;
-}
-
 struct Rec {
     uint32_t w[8];
 };
 
-__host__ __device__ constexpr uint32_t pk4(const char *s, uint32_t n, uint32_t w) {
-    return (4 * w + 0 < n ? (uint32_t)(uint8_t)s[4 * w + 0] : 0u) | (4 * w + 1 < n ? (uint32_t)(uint8_t)s[4 * w + 1] << 8 : 0u) |
-           (4 * w + 2 < n ? (uint32_t)(uint8_t)s[4 * w + 2] << 16 : 0u) |
-           (4 * w + 3 < n ? (uint32_t)(uint8_t)s[4 * w + 3] << 24 : 0u);
-}
 #define GL_CMD(lit) (clen == sizeof(lit) - 1 && c0 == pk4(lit, sizeof(lit) - 1, 0) && c1 == pk4(lit, sizeof(lit) - 1, 1))
 
 // memcached text (text/parser.go:98-171): tokens of bytes.Fields(first line),
@@ -80,25 +57,17 @@ __device__ __forceinline__ void mc_text_log(const uint8_t *b, uint32_t len, uint
     for (uint32_t p = 0; p < len;) {
         const uint32_t c = rd(W, p);
         const bool end = c == '\r' && p + 1 < len && rd(W, p + 1) == '\n';
-        uint32_t w = 1;
-        bool sp = end;
-        if (c < 0x80) {
-            sp = sp || c - 9u < 5u || c == ' ';
-        } else if (c == 0xC2) {  // U+0085, U+00A0
-            if (p + 1 < len) {
-                const uint32_t c1 = rd(W, p + 1);
-                if (c1 == 0x85 || c1 == 0xA0) { sp = true; w = 2; }
-            }
-        } else if (c >= 0xE1 && c <= 0xE3 && p + 2 < len) {
-            // U+1680; U+2000-200A, U+2028, U+2029, U+202F, U+205F; U+3000
+        // a separator (text_bytes.h): the bytes after a lead byte are read where the request holds them
+        uint32_t sw = 0;
+        if (c < 0x80) sw = ws_rune_len(c, 0, 0, 1);
+        else if (ws_lead_len(c) == 2) {
+            if (p + 1 < len) sw = ws_rune_len(c, rd(W, p + 1), 0, 2);
+        } else if (ws_lead_len(c) == 3 && p + 2 < len) {
             const uint32_t c1 = rd(W, p + 1), c2 = rd(W, p + 2);
-            if ((c == 0xE1 && c1 == 0x9A && c2 == 0x80) || (c == 0xE3 && c1 == 0x80 && c2 == 0x80) ||
-                (c == 0xE2 && ((c1 == 0x80 && ((c2 >= 0x80 && c2 <= 0x8A) || c2 == 0xA8 || c2 == 0xA9 || c2 == 0xAF)) ||
-                               (c1 == 0x81 && c2 == 0x9F)))) {
-                sp = true;
-                w = 3;
-            }
+            sw = ws_rune_len(c, c1, c2, 3);
         }
+        const uint32_t w = sw ? sw : 1u;
+        const bool sp = end || sw;
         if (sp && in_tok) {  // token nt is [start, p)
             in_tok = false;
             const uint32_t k = nt++;

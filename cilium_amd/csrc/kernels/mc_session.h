@@ -4,13 +4,13 @@
 // search for a reply line's "\r\n" and for "\r\nEND\r\n" (:203-273), and the
 // element of the forward call's segmented scan.
 //
-// The window is generic_log.hip's, restated so that kernel's code stays as it
-// is: aligned 16-byte loads, never outside [first byte & ~15, (last byte + 16)
-// & ~15) of what the lane walks (include/l7gpu.h: the arena stays readable up
-// to the next 16-byte boundary).
+// The window reads as text_bytes.h's Reader does (aligned 16-byte loads, never
+// outside [first byte & ~15, (last byte + 16) & ~15) of what the lane walks)
+// and holds the 16 bytes as two 64-bit halves: see mcs_rd.
 #pragma once
 #include "../device_tables.h"
 #include "gmem.h"
+#include "text_bytes.h"
 
 namespace l7 {
 
@@ -86,32 +86,20 @@ __device__ __forceinline__ void mcs_tok_add(McTok &t, uint32_t x) {
     else if (j < 12) t.t2 |= v;
     else if (j < 16) t.t3 |= v;
 }
-__host__ __device__ constexpr uint32_t mcs_pk(const char *s, uint32_t n, uint32_t w) {
-    return (4 * w + 0 < n ? (uint32_t)(uint8_t)s[4 * w + 0] : 0u) | (4 * w + 1 < n ? (uint32_t)(uint8_t)s[4 * w + 1] << 8 : 0u) |
-           (4 * w + 2 < n ? (uint32_t)(uint8_t)s[4 * w + 2] << 16 : 0u) |
-           (4 * w + 3 < n ? (uint32_t)(uint8_t)s[4 * w + 3] << 24 : 0u);
-}
 #define MCS_IS(t, lit)                                                                               \
-    ((t).len == sizeof(lit) - 1 && (t).t0 == mcs_pk(lit, sizeof(lit) - 1, 0) &&                      \
-     (t).t1 == mcs_pk(lit, sizeof(lit) - 1, 1) && (t).t2 == mcs_pk(lit, sizeof(lit) - 1, 2) &&       \
-     (t).t3 == mcs_pk(lit, sizeof(lit) - 1, 3))
+    ((t).len == sizeof(lit) - 1 && (t).t0 == pk4(lit, sizeof(lit) - 1, 0) &&                         \
+     (t).t1 == pk4(lit, sizeof(lit) - 1, 1) && (t).t2 == pk4(lit, sizeof(lit) - 1, 2) &&             \
+     (t).t3 == pk4(lit, sizeof(lit) - 1, 3))
 
 // The width of the Unicode White_Space rune at [p, end) whose first byte is c
-// (unicode.IsSpace, as bytes.Fields splits), 0 = none.
+// (text_bytes.h), 0 = none; the bytes after a lead byte are read where [p, end) holds them.
 __device__ __forceinline__ uint32_t mcs_space(McReader &W, uint32_t c, uint64_t p, uint64_t end) {
-    if (c < 0x80) return (c - 9u < 5u || c == ' ') ? 1u : 0u;
-    if (c == 0xC2) {  // U+0085, U+00A0
-        if (p + 1 < end) {
-            const uint32_t c1 = mcs_rd(W, p + 1);
-            if (c1 == 0x85 || c1 == 0xA0) return 2;
-        }
-    } else if (c >= 0xE1 && c <= 0xE3 && p + 2 < end) {
-        // U+1680; U+2000-200A, U+2028, U+2029, U+202F, U+205F; U+3000
+    if (c < 0x80) return ws_rune_len(c, 0, 0, 1);
+    if (ws_lead_len(c) == 2) {
+        if (p + 1 < end) return ws_rune_len(c, mcs_rd(W, p + 1), 0, 2);
+    } else if (ws_lead_len(c) == 3 && p + 2 < end) {
         const uint32_t c1 = mcs_rd(W, p + 1), c2 = mcs_rd(W, p + 2);
-        if ((c == 0xE1 && c1 == 0x9A && c2 == 0x80) || (c == 0xE3 && c1 == 0x80 && c2 == 0x80) ||
-            (c == 0xE2 && ((c1 == 0x80 && ((c2 >= 0x80 && c2 <= 0x8A) || c2 == 0xA8 || c2 == 0xA9 || c2 == 0xAF)) ||
-                           (c1 == 0x81 && c2 == 0x9F))))
-            return 3;
+        return ws_rune_len(c, c1, c2, 3);
     }
     return 0;
 }
@@ -160,7 +148,7 @@ __device__ __forceinline__ uint32_t mcs_text_request(const McLine &L) {
     const uint32_t pre = t.t0 & 0xFFFFFFu, nt = L.ntok;
     uint32_t cls = MCC_OTHER;
     bool noreply = false, watch = false;
-    if (t.len >= 3 && (pre == mcs_pk("get", 3, 0) || pre == mcs_pk("gat", 3, 0))) {
+    if (t.len >= 3 && (pre == pk4("get", 3, 0) || pre == pk4("gat", 3, 0))) {
         cls = MCC_END;
     } else if (MCS_IS(t, "set") || MCS_IS(t, "add") || MCS_IS(t, "replace") || MCS_IS(t, "append") ||
                MCS_IS(t, "prepend")) {

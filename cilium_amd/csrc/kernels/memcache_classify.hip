@@ -30,6 +30,7 @@
 #include "gmem.h"
 #include "launch.h"
 #include "service.h"
+#include "text_bytes.h"
 
 namespace l7 {
 
@@ -47,37 +48,10 @@ constexpr uint32_t kMcWaveChunk = 64 * kMcSortPer;     // entries a wave orders 
 // 3.27 / 3.24 ms, the mixed 4M stream 0.242 / 0.257 / 0.275 ms; profiles/r5/ab5i_*)
 constexpr int kMcWavesPerSimd = 5;
 
-// 16-byte aligned register window over one request (the arena is readable up
-// to the 16-byte boundary after its last byte; see include/l7gpu.h).
-struct Reader {
-    const uint8_t *b;
-    uint64_t base;
-    uint32_t w0, w1, w2, w3;
-};
-
-__device__ __forceinline__ uint32_t rd(Reader &r, uint32_t i) {
-    const uint64_t a = (uint64_t)(r.b + i);
-    const uint64_t base = a & ~(uint64_t)15;
-    if (base != r.base) {
-        const uint4 v = gload16(base);  // global, not flat (gmem.h)
-        r.w0 = v.x; r.w1 = v.y; r.w2 = v.z; r.w3 = v.w;
-        r.base = base;
-    }
-    const uint32_t k = (uint32_t)(a >> 2) & 3;
-    const uint32_t w = k == 0 ? r.w0 : k == 1 ? r.w1 : k == 2 ? r.w2 : r.w3;
-    return (w >> ((a & 3) * 8)) & 0xFF;
-}
-
-// text command name bytes packed little-endian into 4 words (compile-time)
-__host__ __device__ constexpr uint32_t pk(const char *s, uint32_t n, uint32_t w) {
-    return (4 * w + 0 < n ? (uint32_t)(uint8_t)s[4 * w + 0] : 0u) |
-           (4 * w + 1 < n ? (uint32_t)(uint8_t)s[4 * w + 1] << 8 : 0u) |
-           (4 * w + 2 < n ? (uint32_t)(uint8_t)s[4 * w + 2] << 16 : 0u) |
-           (4 * w + 3 < n ? (uint32_t)(uint8_t)s[4 * w + 3] << 24 : 0u);
-}
+// text command name bytes packed little-endian into 4 words (compile-time: pk4, text_bytes.h)
 #define MC_CMD(id, lit)                                                                                   \
-    if (clen == sizeof(lit) - 1 && cw[0] == pk(lit, sizeof(lit) - 1, 0) && cw[1] == pk(lit, sizeof(lit) - 1, 1) && \
-        cw[2] == pk(lit, sizeof(lit) - 1, 2) && cw[3] == pk(lit, sizeof(lit) - 1, 3))                    \
+    if (clen == sizeof(lit) - 1 && cw[0] == pk4(lit, sizeof(lit) - 1, 0) && cw[1] == pk4(lit, sizeof(lit) - 1, 1) && \
+        cw[2] == pk4(lit, sizeof(lit) - 1, 2) && cw[3] == pk4(lit, sizeof(lit) - 1, 3))                    \
         return id;
 
 // McText id of a command token (engine/mc_groups.h); kMcOther if none.
@@ -186,36 +160,7 @@ __device__ __forceinline__ void classify_cmd(const uint32_t cw[4], uint32_t clen
     else fr = F_BAD;
 }
 
-// ---- SWAR text tokenizer (the common case of the text path)
-// bit i (0..15) set iff byte i of the chunk equals b
-__device__ __forceinline__ uint32_t eq_mask(uint4 w, uint32_t b) {
-    const uint32_t bb = b * 0x01010101u;
-    auto e = [bb](uint32_t x) {
-        const uint32_t t = x ^ bb;
-        return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
-    };
-    auto nib = [](uint32_t s) { return __builtin_amdgcn_ubfe((s >> 7) * 0x204081u, 21, 4); };
-    return nib(e(w.x)) | nib(e(w.y)) << 4 | nib(e(w.z)) << 8 | nib(e(w.w)) << 12;
-}
-// bit i set iff byte i is an ASCII white space (0x09..0x0D or 0x20: unicode.IsSpace below 0x80)
-__device__ __forceinline__ uint32_t ascii_space_mask(uint4 w) {
-    auto sp = [](uint32_t x) {
-        const uint32_t t = x & 0x7F7F7F7Fu;
-        // 0x09..0x0D: t - 0x09 < 5 per byte (no borrow across bytes: t >= 0 and the high bit is clear)
-        const uint32_t ge9 = (t + 0x77777777u) & 0x80808080u;   // t >= 0x09
-        const uint32_t ge14 = (t + 0x72727272u) & 0x80808080u;  // t >= 0x0E
-        const uint32_t tt = t ^ 0x20202020u;
-        const uint32_t is20 = ~(((tt & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | tt) & 0x80808080u;
-        return ((ge9 & ~ge14) | is20) & ~x & 0x80808080u;  // high bit of the byte clear
-    };
-    auto nib = [](uint32_t s) { return __builtin_amdgcn_ubfe((s >> 7) * 0x204081u, 21, 4); };
-    return nib(sp(w.x)) | nib(sp(w.y)) << 4 | nib(sp(w.z)) << 8 | nib(sp(w.w)) << 12;
-}
-__device__ __forceinline__ uint32_t chunk_byte(uint4 w, uint32_t q) {
-    const bool upper = (q & 8) != 0;
-    const uint32_t lo = upper ? w.z : w.x, hi = upper ? w.w : w.y;
-    return __builtin_amdgcn_perm(hi, lo, (q & 7) | 0x0C0C0C00u);
-}
+// ---- SWAR text tokenizer (the common case of the text path; the chunk masks are text_bytes.h's)
 
 // Text command line state
 struct TextLine {
@@ -299,6 +244,8 @@ __device__ __forceinline__ void text_fast(const Image &I, Keys<kCh> &K, const ui
                 const uint32_t c0 = chunk_byte(w, i);
                 const uint32_t c1 = i + 1 < 16 ? chunk_byte(w, i + 1) : chunk_byte(wn, i - 15);
                 const uint32_t c2 = i + 2 < 16 ? chunk_byte(w, i + 2) : chunk_byte(wn, i - 14);
+                // ws_rune_len(c0, c1, c2, len - r) of text_bytes.h, written out: through the
+                // call every instantiation spills more SGPRs (profiles/text_bytes/disassembly_compare.txt)
                 uint32_t L = 0;
                 if (c0 == 0xC2) {
                     if (r + 1 < len && (c1 == 0x85 || c1 == 0xA0)) L = 2;

@@ -59,6 +59,7 @@
 #include "../capi_internal.h"
 #include "../deny_templates.h"
 #include "../kernels/cass_parse.h"
+#include "../kernels/text_bytes.h"
 #include "../regex/unicode_tables.h"
 
 namespace {
@@ -136,24 +137,27 @@ std::mutex g_inst_mu;
 std::map<uint64_t, std::shared_ptr<Instance>> g_instances;
 uint64_t g_last_instance = 0;
 
+}  // namespace
+
 // ---------------------------------------------------------------- bytes.Fields
-// Unicode White_Space rune length at s[i] (unicode.IsSpace), 0 if none; a
-// multi-byte space starts with a UTF-8 lead byte, which is always a rune
-// start, so no decoding context is needed.
+// Unicode White_Space rune length at s[i] (unicode.IsSpace), 0 if none: the
+// rule of kernels/text_bytes.h.  A multi-byte space starts with a UTF-8 lead
+// byte, which is always a rune start, so no decoding context is needed; the
+// bytes after it are read where s[0, n) holds them.  Outside the anonymous
+// namespace, and so exported by the library, for one caller besides Fields:
+// tests/native/text_bytes_main.cc, which holds it to ws_rune_len.
+namespace l7 {
 size_t SpaceLen(const uint8_t *s, size_t i, size_t n) {
-    uint8_t c = s[i];
-    if (c == ' ' || (c >= 0x09 && c <= 0x0D)) return 1;
-    if (c < 0xC2 || c > 0xE3 || i + 1 >= n) return 0;
-    uint8_t c1 = s[i + 1];
-    if (c == 0xC2) return (c1 == 0x85 || c1 == 0xA0) ? 2 : 0;
-    if (i + 2 >= n) return 0;
-    uint8_t c2 = s[i + 2];
-    if (c == 0xE1) return (c1 == 0x9A && c2 == 0x80) ? 3 : 0;
-    if (c == 0xE2 && c1 == 0x80) return ((c2 >= 0x80 && c2 <= 0x8A) || c2 == 0xA8 || c2 == 0xA9 || c2 == 0xAF) ? 3 : 0;
-    if (c == 0xE2 && c1 == 0x81) return c2 == 0x9F ? 3 : 0;
-    if (c == 0xE3) return (c1 == 0x80 && c2 == 0x80) ? 3 : 0;
-    return 0;
+    const uint32_t c = s[i], need = ws_lead_len(c);
+    if (!need) return ws_rune_len(c, 0, 0, 1);
+    if (i + need > n) return 0;
+    return ws_rune_len(c, s[i + 1], need == 3 ? s[i + 2] : 0, need);
 }
+}  // namespace l7
+
+namespace {
+
+using l7::SpaceLen;
 
 std::vector<std::string> Fields(const uint8_t *s, size_t n) {
     std::vector<std::string> out;

@@ -418,3 +418,81 @@ def test_frame_streams_http_length_line_at_window_edges(engine, oracle):
     streams = (conns, list(reqs), [[0] for _ in reqs])
     n, whole, frames = _run(engine, oracle, base, max_frames=4, streams=streams, align=16)
     assert frames >= 2 * n - sum(1 for r in reqs if b"Transfer" in r)
+
+
+def _long_line_streams():
+    """memcached text streams whose first command line does not fit the wave
+    framer's first 1 KiB window (the byte-by-byte tokenizer of tnext_mc_text),
+    with one token boundary on the window's edge: `get` and keys up to stream
+    offset 1021, 1022, 1023 or 1024, there one entry of the edge corpus' wide
+    separators (true separators), lone or cut lead bytes and near misses (key
+    bytes), a last key and the line end; and storage lines whose byte count
+    (tokens[4]) lies past offset 1024.  Every stream goes on with a short
+    request, so the long frame's end shows.  Returns (streams, true: the
+    stream's edge entry is a separator or it is a storage line, the wide
+    separator each stream holds or None)."""
+    import mc_edge_cases as E
+    streams, true, wide = [], [], []
+
+    def keys(n):  # n bytes of 199-byte keys and single spaces, a key byte last
+        return bytes(0x20 if k % 200 == 199 and k != n - 1 else 0x61 + k % 26 for k in range(n))
+
+    for entries, is_sep in ((E.WIDE_SPACES, True), (E.LEADS, False), (E.NEAR[:3], False)):
+        for e in entries:
+            for at in (1021, 1022, 1023, 1024):
+                line = b"get " + keys(at - 4) + e + b"user:1\r\n"
+                assert line.index(e + b"user:1") == at
+                streams.append(line + b"get user:1\r\n")
+                true.append(is_sep)
+                wide.append(e if is_sep else None)
+    for klen in (1017, 1018, 1019, 1020):  # "set <key> 0 0 3": tokens[4] at 9 + klen > 1024
+        line = b"set " + bytes(0x61 + k % 26 for k in range(klen)) + b" 0 0 3\r\n"
+        assert line.index(b" 3\r\n") + 1 > 1024
+        streams.append(line + b"abc\r\n" + b"get user:1\r\n")
+        true.append(True)
+        wide.append(None)
+    return streams, true, wide
+
+
+def test_frame_streams_memcached_line_over_a_window(engine, oracle):
+    """A command line longer than a window is tokenized byte by byte, by the
+    White_Space rule of kernels/text_bytes.h as frame.hip writes it out: wide
+    separators, lead bytes and near misses on the first window's last bytes
+    and the next one's first, and a storage line whose byte count lies in the
+    second window.  The oracle's walk frames the short request after every
+    line that a true separator splits, so a framer that stopped at the long
+    line, or read its byte count wrong, fails."""
+    import mc_edge_cases as E
+    streams, true, wide = _long_line_streams()
+    assert len(streams) < 100
+    assert {w for w in wide if w} == set(E.WIDE_SPACES)  # each wide separator is in the set
+    conns = E.conns()
+    text_conn = 1
+    assert int(conns["flags"][text_conn]) == 1
+    base = gen.Workload("mc-long-lines", *gen.pack(streams), np.full(len(streams), text_conn, np.uint32), conns,
+                        gen.mc_policy())
+    s_conns = [text_conn] * len(streams)
+    owalk, _ = _oracle_walk(oracle.Policy(base.policy), base.conns, streams, s_conns, 4)
+    for s, st in enumerate(streams):
+        if true[s]:
+            assert len(owalk[s]) >= 2 and owalk[s][1] == st.index(b"\r\n") + (7 if st.startswith(b"set") else 2), (s, owalk[s])
+    n, whole, frames = _run(engine, oracle, base, max_frames=4, streams=(s_conns, list(streams), [[0] for _ in streams]),
+                            align=16)
+    assert n == len(streams) and frames == sum(len(o) for o in owalk) and frames >= 2 * sum(true)
+
+
+def test_frame_streams_memcached_both_parser_flags(engine, oracle):
+    """A memcached connection with both parser flags set is read as text by the
+    classifier (only L7G_CONN_MC_BINARY alone is binary), and framed as text."""
+    import mc_edge_cases as E
+    conns = E.conns().copy()
+    text_conn = 1
+    conns["flags"][text_conn] = 3
+    streams = [b"get user:1\r\nset cache:1 0 0 3\r\nabc\r\nget user:1\r\n", b"get user:1 user:1\r\nget us",
+               _long_line_streams()[0][0]]
+    base = gen.Workload("mc-both-flags", *gen.pack(streams), np.full(len(streams), text_conn, np.uint32), conns,
+                        gen.mc_policy())
+    s_conns = [text_conn] * len(streams)
+    n, whole, frames = _run(engine, oracle, base, max_frames=4, streams=(s_conns, list(streams), [[0] for _ in streams]),
+                            align=16)
+    assert frames == 3 + 2 + 2

@@ -1,5 +1,7 @@
-"""The stream framer (kernels/frame.hip: its own copy of the memcached SWAR
-tokenizer) on the directed edge corpus of tests/mc_edge_cases.py.
+"""The stream framer (kernels/frame.hip: frame_text_kernel's separator masks
+and byte-wise tokenizer, which write out the White_Space rule of
+kernels/text_bytes.h; frame_streams_kernel's binary headers) on the directed edge corpus of
+tests/mc_edge_cases.py.
 
 Streams are built from the corpus requests that the oracle frames completely
 inside their buffer (ALLOW or DENY with consumed <= len) in families A, B, C,
