@@ -71,7 +71,7 @@ static int dec(const uint8_t *s, size_t n, int32_t *r) {
     else if (b0 >= 0xF0 && b0 <= 0xF4) { sz = 4; if (b0 == 0xF0) lo = 0x90; if (b0 == 0xF4) hi = 0x8F; }
     else { *r = 0xFFFD; return 1; }
     if (n < (size_t)sz || s[1] < lo || s[1] > hi) { *r = 0xFFFD; return 1; }
-    int32_t v = b0 & (0x7F >> (sz + 1));
+    int32_t v = b0 & (0x7F >> sz);  /* payload bits of the lead: 5, 4, 3 */
     v = v << 6 | (s[1] & 0x3F);
     for (int k = 2; k < sz; k++) {
         if (s[k] < 0x80 || s[k] > 0xBF) { *r = 0xFFFD; return 1; }

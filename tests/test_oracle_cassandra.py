@@ -107,6 +107,11 @@ DERIVED = [
     ("", "İNSERT İNTO T", (0, "insert", ".t")),              # U+0130 -> i
     ("", "select * from t", (0, "select", ".t")),                  # U+00A0 is a space
     ("", "select * from ÉTÀ", (0, "select", ".étà")),
+    # lead bytes D0-DF, E8-EF: the decoder once dropped the lead's top payload bit
+    ("", "select * from Дб", (0, "select", ".дб")),                      # U+0414 lowers to U+0434
+    ("", "select * from a\ub000b", (0, "select", ".a\ub000b")),          # U+B000 is not U+3000, a space
+    ("", "select * from a\u0485b", (0, "select", ".a\u0485b")),          # U+0485 is not U+0085, a space
+    ("", "SELECT * FROM t\ufeff", (0, "select", ".t\ufeff")),            # re-encoded after the 'S': EF BB BF
 ]
 
 
