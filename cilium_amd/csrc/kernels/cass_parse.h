@@ -316,7 +316,7 @@ L7_HD inline void cass_seg3(const CassQuery &Q, const uint8_t *q, const uint8_t 
         cass_emit(q, Q.ts, Q.te, Q.fc, lower, nlower, sink);
     } else if (Q.seg3 == S3_KS_TABLE) {
         if (ks && cass_emit(ks, ks_s, ks_e, ks_fc, lower, nlower, sink)) return;  // '/' in the keyspace
-        sink.raw('.');
+        sink.rune('.');  // (a rune, not a kept invalid byte: the NFA sink reads raw() as U+FFFD)
         cass_emit(q, Q.ts, Q.te, Q.fc, lower, nlower, sink);
     }
 }
